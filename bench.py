@@ -15,7 +15,17 @@ Multi-GPU (torchrun, one rank per GPU): reads shard embarrassingly -- every rank
 index replica and its own 50M-read shard (weak scaling: 8 GPUs = configs[3]'s 400M reads); the
 only collectives are the timing barrier and the max-over-ranks.
 
-Extra JSON fields (rank 0, N=1):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line: `value`, `ms_per_step`, and under `extra` what the timed steps' own HIP
+events and counters give (kernel_ms_per_step, device memory, build_id).  Everything that takes runs
+of its own is behind `--full`; the options that size or switch off single legs (--no-cpu,
+--exact-leg, --sa2pos, --e2e-leg, --e2e-gz, --sw-leg, --ref-budget) act under `--full` only.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of ibwa_batch_fetch
+receives it, to DIR/<name>.npy (see dump_outputs); the inputs depend on the arguments alone, so two
+builds run with the same arguments can be compared file by file.
+
+Extra JSON fields with `--full` (rank 0, N=1):
   roofline      -- algorithmic bytes (64 B x Occ-interval touches per read, counted by the CPU
                    restatement on the measured reads) over the step's kernel time (HIP events);
                    `traffic` = HBM bytes per step from the committed rocprofv3 PMC profile of
@@ -631,7 +641,44 @@ def sw_leg(eng, refs, reads, do_cpu, steps=3):
     return out
 
 
-def main():
+DUMP_READS = 500_000  # reads sampled by --dump-outputs (n_aln.npy: 2 MB)
+DUMP_HITS = 1_500_000  # hit rows kept of the sampled reads (alns.npy: 48 MB)
+DUMP_SEED = 11
+
+
+def dump_outputs(d, n_aln, alns, rank, world):
+    """--dump-outputs: the hits of the last timed step (ibwa_batch_fetch: per-read counts and the
+    bwt_aln1_t records back to back), at most 64 MB in all:
+      summary.npy  float64 [reads, hits, reads with a hit, and the sums of k, l, score and info
+                   modulo 2^40] over the whole batch (each exact in float64)
+      read_ids.npy float64, the reads sampled: all if at most DUMP_READS, else DUMP_READS ids drawn
+                   with a fixed seed (the same for a given batch size), ascending
+      n_aln.npy    float32, hits of each sampled read
+      alns.npy     float64 [rows, 4] = (info, k, l, score) of the sampled reads' hits, in read order,
+                   the first DUMP_HITS rows
+    Under torchrun every rank writes its own shard's files, <name>.rank<r>.npy."""
+    os.makedirs(d, exist_ok=True)
+    n = n_aln.size
+    if n > DUMP_READS:
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_READS, replace=False))
+    else:
+        ids = np.arange(n, dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(n_aln, dtype=np.int64)[:-1]])[ids]
+    cnt = n_aln[ids].astype(np.int64)
+    # row numbers of the sampled reads' hits, read by read
+    start = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    rows = np.repeat(first - start, cnt) + np.arange(int(cnt.sum()), dtype=np.int64)
+    h = alns[rows[:DUMP_HITS]]
+    out = {"summary": np.array([n, alns.size, int((n_aln > 0).sum())] +
+                               [int(alns[f].astype(np.uint64).sum(dtype=np.uint64)) & ((1 << 40) - 1)
+                                for f in ("k", "l", "score", "info")], dtype=np.float64),
+           "read_ids": ids.astype(np.float64), "n_aln": cnt.astype(np.float32),
+           "alns": np.stack([h[f].astype(np.float64) for f in ("info", "k", "l", "score")], axis=1)}
+    for name, a in out.items():
+        np.save(os.path.join(d, name + (".npy" if world == 1 else f".rank{rank}.npy")), a)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -663,7 +710,20 @@ def main():
     ap.add_argument("--shards", type=int, default=1,
                     help="single process: align the reads of ranks 0..K-1 as one batch (checks the sharded path)")
     ap.add_argument("--dump", default="", help="write this rank's hits to DUMP.rank<r>.npz after the timed steps")
-    args = ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's hits (a fixed sample of a large batch) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines and parity, the rooflines, "
+                         "and the sa2pos, SW, exact and end-to-end legs")
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu = True
+        args.exact_leg = args.sa2pos = args.e2e_leg = args.sw_leg = 0
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -758,9 +818,13 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     dt = reduce_max(dt, dist, red_dev)
-    if args.dump:
+    if args.dump or args.dump_outputs:
         n_d, a_d = eng.fetch()
-        np.savez(f"{args.dump}.rank{rank}.npz", n_aln=n_d, alns=a_d.view(np.uint32))
+        if args.dump:
+            np.savez(f"{args.dump}.rank{rank}.npz", n_aln=n_d, alns=a_d.view(np.uint32))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, n_d, a_d, rank, world)
+        del n_d, a_d
     # device memory held once the timed steps ran (index, tables and this context's search buffers)
     free_b, total_b = ctypes.c_size_t(0), ctypes.c_size_t(0)
     hip.hipMemGetInfo(ctypes.byref(free_b), ctypes.byref(total_b))

@@ -5,6 +5,8 @@
 #      by size and the DRAM-bound share, per dispatch
 # then tools/profile_summary.py writes profiles/<round>_<tag>_{kernel_stats.csv,pmc.json}.
 # usage: tools/profile_round.sh <round> <tag> <bench args...>
+# The exact leg's kernels (k_exact, k_pack_reads) are profiled only where the bench args hold
+# --full (with --no-cpu --sa2pos 0 --sw-leg 0 --e2e-leg 0 to keep the other legs out).
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp

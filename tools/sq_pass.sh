@@ -1,6 +1,6 @@
 #!/bin/bash
 # One SQ-counter rocprofv3 pass over a short gapped bench (issue vs wait breakdown per kernel).
-# usage: tools/sq_pass.sh <tag> <bench args...>
+# usage: tools/sq_pass.sh <tag> <bench args...>   (k_exact, k_sw: only with --full among them)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
