@@ -813,6 +813,7 @@ int ibwa_ctx_load_bwt(ibwa_ctx_t *c, int strand, uint32_t primary, const uint32_
   ix.L2[0] = 0;
   for (int j = 0; j < 4; ++j) ix.L2[j + 1] = L2[j];
   c->loaded[strand] = true;
+  c->build_rounds[strand] = 0;
   c->kmer_valid = false;
   c->jump_ready = false;  // SA / ISA / text belong to an index built here (or are derived again)
   c->jump_derived = false;
@@ -853,6 +854,7 @@ int ibwa_ctx_clone_index(ibwa_ctx_t *dst, const ibwa_ctx_t *src) {
     dst->ix[s] = src->ix[s];
     dst->ix[s].blk = dst->idx[s].as<uint4>();
     dst->loaded[s] = true;
+    dst->build_rounds[s] = src->build_rounds[s];
     dst->kmer_valid = false;
     dst->sa_loaded[s] = false;
   }
@@ -1013,6 +1015,13 @@ int ibwa_ctx_export_sa(const ibwa_ctx_t *c, int strand, uint32_t *out, uint64_t 
   HIPCHK(enter(c));
   HIPCHK(hipMemcpy(out, c->sa_s[strand].p, n_sa * 4, hipMemcpyDeviceToHost));
   out[0] = 0xFFFFFFFFu;  // bwt.c:66
+  return 0;
+}
+
+int ibwa_ctx_build_rounds(const ibwa_ctx_t *c, int strand, int *rounds) {
+  if (strand < 0 || strand > 1 || !c->loaded[strand] || !c->build_rounds[strand])
+    return fail(IBWA_ENOINDEX, "no index built here");
+  if (rounds) *rounds = c->build_rounds[strand];
   return 0;
 }
 

@@ -322,7 +322,8 @@ hipError_t build_strand(const uint8_t *T, uint64_t n, uint4 *out_blocks, uint32_
   HC(hipMalloc(&S.rank, N * 4));
   HC(hipMalloc(&S.v1, N * 4));
   HC(hipMalloc(&S.k0, N * 8));
-  HC(hipMalloc(&S.k1, N * 8));
+  // k1 also holds the per-block counts and their prefix (2 x uint4 per block): more than N * 8 below 7 symbols
+  HC(hipMalloc(&S.k1, std::max<uint64_t>(N * 8, ((n + 127) / 128 + 1) * 32)));
   // temp storage: the largest of the rocPRIM calls at size N
   {
     size_t a = 0, b = 0, c = 0;

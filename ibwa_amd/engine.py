@@ -121,6 +121,7 @@ CAPI = {
     "ibwa_ctx_bwt_info": (_i, [_vp, _i, c.POINTER(_u32), c.POINTER(_u32), c.POINTER(_u64)]),
     "ibwa_ctx_export_bwt": (_i, [_vp, _i, _vp, _u64]),
     "ibwa_ctx_export_sa": (_i, [_vp, _i, _vp, _u64]),
+    "ibwa_ctx_build_rounds": (_i, [_vp, _i, c.POINTER(_i)]),
     "ibwa_sw_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p),
                            c.POINTER(_i64)]),
     "ibwa_global_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, c.POINTER(c.c_void_p),
@@ -328,6 +329,12 @@ class Engine:
         out = np.zeros((n + intv) // intv, dtype=np.uint32)
         _chk(lib().ibwa_ctx_export_sa(self.h, strand, out.ctypes.data, out.size))
         return out
+
+    def build_rounds(self, strand):
+        """Sort rounds build_index took for this strand (prefix doubling from 21 symbols)."""
+        r = c.c_int()
+        _chk(lib().ibwa_ctx_build_rounds(self.h, strand, c.byref(r)))
+        return r.value
 
     def load_sa_files(self, prefix):
         """bwt_restore_sa (bwtio.c:29) of prefix.sa / prefix.rsa onto the device."""

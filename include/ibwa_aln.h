@@ -322,6 +322,9 @@ int ibwa_ctx_export_bwt(const ibwa_ctx_t *ctx, int strand, uint32_t *words, uint
 /* Export the sampled SA kept by ibwa_ctx_build_index: out[(n+intv)/intv] with out[0] = (u32)-1
  * (bwt.c:56-66); entries 1.. are what bwt_dump_sa writes. */
 int ibwa_ctx_export_sa(const ibwa_ctx_t *ctx, int strand, uint32_t *out, uint64_t cap);
+/* Sort rounds the last ibwa_ctx_build_index took for a strand (prefix doubling: round r compares
+ * 21 * 2^(r-1) symbols); an error for an index that was loaded, not built. */
+int ibwa_ctx_build_rounds(const ibwa_ctx_t *ctx, int strand, int *rounds);
 
 /*
  * Batched Smith-Waterman with path: aln_local_core (stdaln.c:529-760) with

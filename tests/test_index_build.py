@@ -53,6 +53,29 @@ def test_device_index_is_bit_identical(golden_dir):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("prefix", ["tandem", "stale", "stale_alt", "remap_alt"])
+def test_device_index_of_paired_fixtures(golden_dir, prefix):
+    """The small reference-built indexes of the paired fixtures (stale_alt: 300 bp; tandem: long
+    tandem repeats), built on the device from their .pac and compared with .bwt/.rbwt/.sa/.rsa."""
+    import oracle
+    codes, l_pac = oracle.read_pac(os.path.join(golden_dir, prefix))
+    eng = E.Engine(0)
+    eng.build_index(codes, sa_intv=32)
+    for s, (ext, sext) in enumerate([("bwt", "sa"), ("rbwt", "rsa")]):
+        primary, L2, words = E.read_bwt_file(os.path.join(golden_dir, f"{prefix}.{ext}"))
+        p, l2, w = eng.export_bwt(s)
+        assert p == primary and tuple(l2) == tuple(L2) and L2[3] == l_pac, ext
+        assert w.size == words.size and (w == words).all(), ext
+        raw = open(os.path.join(golden_dir, f"{prefix}.{sext}"), "rb").read()
+        hdr = struct.unpack("<7I", raw[:28])
+        assert hdr == (primary,) + tuple(L2) + (32, l_pac), sext
+        ref_sa = np.frombuffer(raw[28:], dtype=np.uint32)
+        got = eng.export_sa(s, 32)
+        assert got.size == ref_sa.size + 1 and (got[1:] == ref_sa).all(), sext
+    eng.close()
+
+
+@pytest.mark.gpu
 def test_device_index_aligns_like_file_index(golden_dir, sai_manifest):
     import oracle
     eng = E.Engine(0)

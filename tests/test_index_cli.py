@@ -1,7 +1,9 @@
 """`ibwa-amd index` / `fa2pac` / `pac_rev` (index_main.cpp) against the reference's `bwa index`
 output, byte for byte: tests/golden/idx_quirks.* (tools/make_index_golden.py: IUPAC holes,
 stale kseq comments, CRLF, empty record) and tests/golden/g1m.* (the golden genome, regenerated
-from synth.cpp and written as FASTA).  fa2pac / pac_rev run on the CPU; `index` sorts on the GPU."""
+from synth.cpp and written as FASTA), and the small indexes of the paired fixtures (tandem, stale,
+the 300 bp stale_alt, remap_alt) from their committed FASTA.  fa2pac / pac_rev run on the CPU;
+`index` sorts on the GPU."""
 import os
 import subprocess
 
@@ -13,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "ibwa_amd", "bin", "ibwa-amd")
 PACK_EXTS = ("pac", "ann", "amb", "rpac")
 ALL_EXTS = PACK_EXTS + ("bwt", "rbwt", "sa", "rsa")
+PAIRED_FIXTURES = ("tandem", "stale", "stale_alt", "remap_alt")
 
 
 def _g1m_fasta(path):
@@ -34,10 +37,12 @@ def _same(a, b):
 def fastas(tmp_path_factory, golden_dir):
     d = tmp_path_factory.mktemp("fa")
     _g1m_fasta(str(d / "g1m.fa"))
-    return {"idx_quirks": os.path.join(golden_dir, "idx_quirks.fa"), "g1m": str(d / "g1m.fa")}
+    out = {nm: os.path.join(golden_dir, nm + ".fa") for nm in ("idx_quirks",) + PAIRED_FIXTURES}
+    out["g1m"] = str(d / "g1m.fa")
+    return out
 
 
-@pytest.mark.parametrize("name", ["idx_quirks", "g1m"])
+@pytest.mark.parametrize("name", ["idx_quirks", "g1m"] + list(PAIRED_FIXTURES))
 def test_fa2pac_and_pac_rev(fastas, golden_dir, name, tmp_path):
     pre = str(tmp_path / "x")
     r = subprocess.run([CLI, "fa2pac", fastas[name], pre], capture_output=True, text=True, timeout=120)
@@ -56,7 +61,7 @@ def test_index_rejects_color_space_and_unknown_algorithm(fastas, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["idx_quirks", "g1m"])
+@pytest.mark.parametrize("name", ["idx_quirks", "g1m"] + list(PAIRED_FIXTURES))
 def test_index_matches_reference(fastas, golden_dir, name, tmp_path):
     pre = str(tmp_path / "x")
     r = subprocess.run([CLI, "index", "-a", "bwtsw", "-p", pre, fastas[name]], capture_output=True, text=True,

@@ -121,6 +121,58 @@ def test_aln_pe_reads_match_reference_sai(golden_dir, key, tmp_path):
         assert oracle.sai_body_equal(out.read_bytes(), open(os.path.join(golden_dir, sai), "rb").read())
 
 
+def _sampe_only_sai():
+    """(prefix, [.sai of end 1, end 2], [reads of end 1, end 2]) of the reference `aln` outputs
+    (default options) that are otherwise only ever inputs to sampe: the stale and remap manifests'
+    two references each, and the tandemt reads on the tandem index."""
+    stale = json.load(open(os.path.join(ROOT, "tests", "golden", "stale_manifest.json")))["stale.R.t1"]
+    remap = REMAP["remap.R"]
+    out = [(pre, sai, m["reads"]) for m in (stale, remap) for pre, sai in zip(m["prefixes"], m["sai"])]
+    t = MANIFEST["tandemt.R"]
+    assert t["aln_argv"] == []
+    out.append((t["prefix"], t["sai"], t["reads"]))
+    return out
+
+
+SAMPE_ONLY_SAI = _sampe_only_sai()
+
+
+@pytest.mark.parametrize("prefix,sai,reads", SAMPE_ONLY_SAI, ids=[x[1][0][:-6] for x in SAMPE_ONLY_SAI])
+def test_aln_writes_the_sampe_only_reference_sai(golden_dir, prefix, sai, reads, tmp_path):
+    """`ibwa-amd aln` with default options reproduces stale_stale, stale_stale_alt (70 bp reads on a
+    300 bp genome), remap_g1m, remap_remap_alt and tandemt, each end byte for byte."""
+    import oracle
+    for s, rd in zip(sai, reads):
+        out = tmp_path / "out.sai"
+        r = subprocess.run([CLI, "aln", "-f", str(out), os.path.join(golden_dir, prefix), os.path.join(golden_dir, rd)],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert oracle.sai_body_equal(out.read_bytes(), open(os.path.join(golden_dir, s), "rb").read()), s
+
+
+@pytest.mark.parametrize("prefix,sai,reads", [x for x in SAMPE_ONLY_SAI if x[0] in ("stale_alt", "remap_alt")],
+                         ids=["stale_alt", "remap_alt"])
+def test_small_reference_sai_through_the_heavy_pass(golden_dir, prefix, sai, reads):
+    """The same reads on the two small alternate references through the engine with an iteration
+    budget of 1 (every gapped read goes to the cooperative pass): the reference's .sai bytes."""
+    import oracle
+    from ibwa_amd import engine as E
+    eng = E.Engine(0)
+    eng.load_index_files(os.path.join(golden_dir, prefix))
+    eng.set_option("gap_iter_budget", 1)
+    opt, _ = oracle.parse_aln_args([])
+    hits = 0
+    for s, rd in zip(sai, reads):
+        recs = oracle.read_fastq_records(os.path.join(golden_dir, rd))
+        seqs, offs, lens = oracle.encode_reads(recs, opt.mode, opt.trim_qual)
+        n_aln, alns = eng.aln(seqs, offs, lens, E.default_opt())
+        hits += int(n_aln.sum())
+        exp = open(os.path.join(golden_dir, s), "rb").read()
+        assert oracle.sai_body_equal(oracle.sai_bytes(opt, n_aln, alns), exp), s
+    assert hits > 0  # (end 1 of the stale reads has no hit on stale_alt; end 2 has)
+    eng.close()
+
+
 @pytest.mark.parametrize("aln_opts", [["-B", "5"], ["-I", "-q", "15"], []])
 def test_sampe_bulk_reader_equals_serial(golden_dir, aln_opts, tmp_path):
     """sampe's reads come from the bulk FASTQ parser on host threads (sampe_main.cpp Source::take,
