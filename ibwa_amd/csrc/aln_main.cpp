@@ -9,6 +9,11 @@
 // in input order.  Added: -G INT (number of GPUs; a batch is split into
 // contiguous slices that keep the batch-level max length, bwtaln.c:89-93).
 // Reading the next batch overlaps the GPU work on the current one.
+//
+// Pair mode, `ibwa-amd aln [options] -f <out1.sai> -F <out2.sai> <prefix> <in1.fq> <in2.fq>` (with
+// -b: one BAM, its first reads to -f and its second reads to -F): both ends of a pair aligned by one
+// process -- one device arena, one index load, the lanes shared -- each output the bytes of a
+// single-input run on that input.  -F selects it; without -F nothing changes.
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -256,7 +261,9 @@ int read_group(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, Batch &g, B
 }
 
 void usage(const ibwa_gap_opt_t *o) {
-  fprintf(stderr, "\nUsage:   ibwa-amd aln [options] <prefix> <in.fq>\n\n");
+  fprintf(stderr, "\nUsage:   ibwa-amd aln [options] <prefix> <in.fq>\n");
+  fprintf(stderr, "         ibwa-amd aln [options] -f <out1.sai> -F <out2.sai> <prefix> <in1.fq> <in2.fq>\n");
+  fprintf(stderr, "         ibwa-amd aln [options] -b -f <out1.sai> -F <out2.sai> <prefix> <in.bam>\n\n");
   fprintf(stderr, "Options: -n NUM    max #diff (int) or missing prob under 0.02 err rate (float) [%.2f]\n", o->fnr);
   fprintf(stderr, "         -o INT    maximum number or fraction of gap opens [%d]\n", o->max_gapo);
   fprintf(stderr, "         -e INT    maximum number of gap extensions, -1 for disabling long gaps [-1]\n");
@@ -273,6 +280,8 @@ void usage(const ibwa_gap_opt_t *o) {
   fprintf(stderr, "         -R INT    stop searching when there are >INT equally best hits [%d]\n", o->max_top2);
   fprintf(stderr, "         -q INT    quality threshold for read trimming down to %dbp [%d]\n", kMinRdLen, o->trim_qual);
   fprintf(stderr, "         -f FILE   file to write output to instead of stdout\n");
+  fprintf(stderr, "         -F FILE   pair mode: the second input's output (<in2.fq>, or with -b the BAM's second reads;\n");
+  fprintf(stderr, "                   the first input's goes to -f)\n");
   fprintf(stderr, "         -B INT    length of barcode\n");
   fprintf(stderr, "         -c        input sequences are in the color space\n");
   fprintf(stderr, "         -L        log-scaled gap penalty for long deletions\n");
@@ -285,11 +294,23 @@ int die(const char *what) {
   return 1;
 }
 
+// One input of a run and what belongs to it alone: its reader, its output, and the options written as
+// its .sai header (BAM pair mode: the mode bits that -1 / -2 would have set).  A run has one of them,
+// or two in pair mode (-F); everything on the GPUs is shared (run_aln).
+template <class Reader>
+struct AlnInput {
+  Reader *rd = nullptr;
+  FastqBulk *fb = nullptr;       // the threaded host parser (null: the serial reader only, BAM)
+  const char *fq_dev = nullptr;  // the file the GPUs parse (null: the host readers from the start)
+  const char *fq_path = nullptr;
+  const char *fn_out = nullptr;  // null: stdout
+  ibwa_gap_opt_t opt;
+};
+
 }  // namespace
 
 template <class Reader>
-int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::string &prefix, const char *fn_out,
-            int n_gpus, const char *fq_dev, const char *fq_path);
+int run_aln(std::vector<AlnInput<Reader>> &ins, const std::string &prefix, int n_gpus);
 
 int samse_main(int argc, char *argv[]);  // samse_main.cpp
 int sampe_main(int argc, char *argv[]);  // sampe_main.cpp
@@ -310,6 +331,7 @@ int main(int argc, char *argv[]) {
   if (argc >= 2 && strcmp(argv[1], "pac_rev") == 0) return pac_rev_main(argc - 1, argv + 1);
   if (argc < 2 || strcmp(argv[1], "aln") != 0) {
     fprintf(stderr, "Usage: ibwa-amd aln [options] <prefix> <in.fq>\n"
+                    "       ibwa-amd aln [options] -f <out1.sai> -F <out2.sai> <prefix> <in1.fq> <in2.fq>\n"
                     "       ibwa-amd samse [-n max_occ] [-f out.sam] [-r RG] <prefix> <in.sai> <in.fq>\n"
                     "       ibwa-amd sampe [options] <prefix> <in1.sai> <in2.sai> <in1.fq> <in2.fq>\n"
                     "       ibwa-amd index [-a bwtsw|div|is] [-p prefix] <in.fasta>\n"
@@ -320,9 +342,24 @@ int main(int argc, char *argv[]) {
   init_nt4();
   ibwa_gap_opt_t opt;
   int n_gpus = 1;
-  const char *fn_out = nullptr;
-  const int first_arg = ibwa_aln_parse_args(argc, argv, &opt, &n_gpus, &fn_out);  // bwtaln.c:249-284 (+ -G)
+  const char *fn_out = nullptr, *fn_out2 = nullptr;
+  const int first_arg = ibwa_aln_parse_args2(argc, argv, &opt, &n_gpus, &fn_out, &fn_out2);  // bwtaln.c:249-284 (+ -G, -F)
   if (first_arg < 0) return 1;
+  const bool pair = fn_out2 != nullptr;  // -F: both ends in this process
+  if (pair) {
+    const char *bad = nullptr;
+    if (!fn_out) bad = "-F needs -f: stdout can carry only one of the two outputs";
+    else if (!strcmp(fn_out, fn_out2)) bad = "-F and -f name the same file";
+    else if (opt.mode & (IBWA_MODE_BAM_SE | IBWA_MODE_BAM_READ1 | IBWA_MODE_BAM_READ2))
+      bad = "-0, -1 and -2 cannot be combined with -F (-b -F sends the first reads to -f, the second reads to -F)";
+    else if (first_arg + ((opt.mode & IBWA_MODE_BAM) ? 2 : 3) > argc)
+      bad = (opt.mode & IBWA_MODE_BAM) ? "-b -F needs <prefix> <in.bam>" : "-F needs <prefix> <in1.fq> <in2.fq>";
+    if (bad) {
+      fprintf(stderr, "[ibwa-amd aln] %s\n", bad);
+      if (first_arg + 2 > argc) usage(&opt);
+      return 1;
+    }
+  }
   if (first_arg + 2 > argc) {
     usage(&opt);
     return 1;
@@ -341,35 +378,66 @@ int main(int argc, char *argv[]) {
     if (opt.mode & IBWA_MODE_BAM_READ1) which |= 1;
     if (opt.mode & IBWA_MODE_BAM_READ2) which |= 2;
     if (which == 0) which = 7;
-    BamReader rd;
-    if (!rd.open(argv[first_arg + 1], which)) {
-      fprintf(stderr, "[ibwa-amd aln] cannot open %s as BAM\n", argv[first_arg + 1]);
-      return 1;
+    // pair mode: the BAM opened twice, what -1 selects to -f and what -2 selects to -F, each header
+    // with that option's mode bit
+    const int n_in = pair ? 2 : 1;
+    BamReader rd[2];
+    std::vector<AlnInput<BamReader>> ins(n_in);
+    for (int i = 0; i < n_in; ++i) {
+      if (!rd[i].open(argv[first_arg + 1], pair ? 1 + i : which)) {
+        fprintf(stderr, "[ibwa-amd aln] cannot open %s as BAM\n", argv[first_arg + 1]);
+        return 1;
+      }
+      ins[i].rd = &rd[i];
+      ins[i].fq_path = argv[first_arg + 1];
+      ins[i].fn_out = i ? fn_out2 : fn_out;
+      ins[i].opt = opt;
+      if (pair) ins[i].opt.mode |= i ? IBWA_MODE_BAM_READ2 : IBWA_MODE_BAM_READ1;
     }
-    return run_aln(rd, nullptr, opt, prefix, fn_out, n_gpus, nullptr, argv[first_arg + 1]);
-  }
-  SeqReader rd;
-  if (!rd.open(argv[first_arg + 1])) {
-    fprintf(stderr, "[ibwa-amd aln] cannot open %s\n", argv[first_arg + 1]);
-    return 1;
+    return run_aln(ins, prefix, n_gpus);
   }
   // IBWA_ALN_SERIAL_READ=1: the serial reader only (tests compare the two); an uncompressed FASTQ
   // file is parsed on the GPUs (ingest.h) unless IBWA_ALN_GPU_PARSE=0
-  FastqBulk fb(rd);
   const bool serial = env_int("IBWA_ALN_SERIAL_READ", 0) != 0;
   const char *gp = getenv("IBWA_ALN_GPU_PARSE");
-  const bool dev_parse = !serial && !(gp && atoi(gp) == 0) && FastqGpu::usable(argv[first_arg + 1]);
-  return run_aln(rd, serial ? nullptr : &fb, opt, prefix, fn_out, n_gpus, dev_parse ? argv[first_arg + 1] : nullptr,
-                 argv[first_arg + 1]);
+  const int n_in = pair ? 2 : 1;
+  SeqReader rd[2];
+  FastqBulk fb[2] = {FastqBulk(rd[0]), FastqBulk(rd[1])};
+  std::vector<AlnInput<SeqReader>> ins(n_in);
+  for (int i = 0; i < n_in; ++i) {
+    const char *fn = argv[first_arg + 1 + i];
+    if (!rd[i].open(fn)) {
+      fprintf(stderr, "[ibwa-amd aln] cannot open %s\n", fn);
+      return 1;
+    }
+    const bool dev_parse = !serial && !(gp && atoi(gp) == 0) && FastqGpu::usable(fn);
+    ins[i].rd = &rd[i];
+    ins[i].fb = serial ? nullptr : &fb[i];
+    ins[i].fq_dev = dev_parse ? fn : nullptr;
+    ins[i].fq_path = fn;
+    ins[i].fn_out = i ? fn_out2 : fn_out;
+    ins[i].opt = opt;
+  }
+  return run_aln(ins, prefix, n_gpus);
 }
 
+// The inputs (one, or the two of pair mode) share the arena, the contexts, the index and the lanes;
+// each has its own reader, device parse, output and ordered writer, and its groups take turns on the
+// lanes.  One input is the one-element case of the same code.
 template <class Reader>
-int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::string &prefix, const char *fn_out,
-            int n_gpus, const char *fq_dev, const char *fq_path) {
-  FILE *out = fn_out ? fopen(fn_out, "wb") : stdout;
-  if (!out) {
-    fprintf(stderr, "[ibwa-amd aln] cannot write %s\n", fn_out);
-    return 1;
+int run_aln(std::vector<AlnInput<Reader>> &ins, const std::string &prefix, int n_gpus) {
+  const int n_in = (int)ins.size();
+  const bool pair = n_in > 1;
+  const ibwa_gap_opt_t &opt = ins[0].opt;  // the inputs' options differ in the header's BAM bits only
+  // " [in1]" / " [in2]" after a line that is about one input (pair mode; nothing for a single input)
+  auto tag = [pair](int i) { return !pair ? "" : i ? " [in2]" : " [in1]"; };
+  std::vector<FILE *> outs(n_in, nullptr);
+  for (int i = 0; i < n_in; ++i) {
+    outs[i] = ins[i].fn_out ? fopen(ins[i].fn_out, "wb") : stdout;
+    if (!outs[i]) {
+      fprintf(stderr, "[ibwa-amd aln] cannot write %s\n", ins[i].fn_out);
+      return 1;
+    }
   }
   if (n_gpus < 1) n_gpus = 1;
   ibwa_sam::Phases ph;
@@ -413,9 +481,19 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     }
     return (double)st.st_size;
   };
-  const double in_bytes = fastq_bytes(fq_path && strcmp(fq_path, "-") ? fq_path : nullptr);
+  // (pair mode: the two inputs together -- their groups share the lanes, so it is their sum that is
+  // cut into at least two groups per lane, and the pieces of both inputs follow from it)
+  std::vector<double> in_b(n_in, 0.0);
+  double in_bytes = 0.0;
+  bool any_dev = false;
+  for (int i = 0; i < n_in; ++i) {
+    const char *p = ins[i].fq_path;
+    in_b[i] = fastq_bytes(p && strcmp(p, "-") ? p : nullptr);
+    in_bytes += in_b[i];
+    any_dev = any_dev || ins[i].fq_dev;
+  }
   uint64_t piece = pm && atoll(pm) > 0 ? (uint64_t)atoll(pm) : (uint64_t)3 << 29;
-  if (!(pm && atoll(pm) > 0) && fq_dev) {
+  if (!(pm && atoll(pm) > 0) && any_dev) {
     const uint64_t fs = (uint64_t)in_bytes;
     const uint64_t per_lane = (uint64_t)n_lanes * (uint64_t)n_gpus;
     if (fs > 0 && fs <= piece * per_lane)
@@ -441,23 +519,34 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     const double GiB = (double)(1u << 30);
     // FASTQ bytes of one GPU's group: a region's piece (equal regions of at most `piece` per GPU, as
     // FastqGpu cuts them), or (host readers) up to kGroup batches
-    const double fq = in_bytes;
-    double grp_b = (double)kGroup * kSub * 300.0;
-    if (fq_dev) {
-      const double per = (double)piece * n_gpus, n_reg = std::max(1.0, std::ceil(fq / per));
-      grp_b = std::min(per, fq / n_reg) / n_gpus;
-    }
-    const double grp = std::min(fq / n_gpus, grp_b) / GiB;
-    // the read length from the first record (plain FASTQ): longer reads take the larger pool
-    int first_len = 0;
-    if (fq_path && strcmp(fq_path, "-") != 0)
-      if (gzFile f = gzopen(fq_path, "rb")) {  // (plain files are read as they are)
-        char line[4096];
-        if (gzgets(f, line, sizeof line) && line[0] == '@' && gzgets(f, line, sizeof line))
-          first_len = (int)strcspn(line, "\r\n");
-        gzclose(f);
+    // (pair mode: the larger of the two inputs' groups -- a lane holds a group of either input -- and
+    // each input has its own parse scratch and ingest slots)
+    double grp = 0.0, ingest_gb = 0.0;
+    for (int i = 0; i < n_in; ++i) {
+      const double fq = in_b[i];
+      double grp_b = (double)kGroup * kSub * 300.0;
+      if (ins[i].fq_dev) {
+        const double per = (double)piece * n_gpus, n_reg = std::max(1.0, std::ceil(fq / per));
+        grp_b = std::min(per, fq / n_reg) / n_gpus;
       }
-    const bool long_reads = first_len == 0 || first_len > 128;
+      const double g = std::min(fq / n_gpus, grp_b) / GiB;
+      grp = std::max(grp, g);
+      ingest_gb += 1.7 * g + (n_lanes + (pair ? 2 : 3)) * 0.8 * g;
+    }
+    // the read length from the first record (plain FASTQ): longer reads take the larger pool
+    bool long_reads = false;
+    for (int i = 0; i < n_in; ++i) {
+      const char *fq_path = ins[i].fq_path;
+      int first_len = 0;
+      if (fq_path && strcmp(fq_path, "-") != 0)
+        if (gzFile f = gzopen(fq_path, "rb")) {  // (plain files are read as they are)
+          char line[4096];
+          if (gzgets(f, line, sizeof line) && line[0] == '@' && gzgets(f, line, sizeof line))
+            first_len = (int)strcspn(line, "\r\n");
+          gzclose(f);
+        }
+      long_reads = long_reads || first_len == 0 || first_len > 128;
+    }
     const double fixed = long_reads ? 36.0 : 30.0, per_gib = long_reads ? 20.0 : 21.5;
     // the first pass's level tables (engine gap_tab_k): 2 x 8 B x ((4^(K+2) - 1) / 3) for the K that
     // strings of length K + 1 still mostly occur at, at most 13 (5.7 GB for a GRCh37-sized genome; the
@@ -469,8 +558,7 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     cli_tab_k = tab_k;
     const double ltab_gb = tab_k ? 2.0 * 8.0 * (std::ldexp(1.0, 2 * (tab_k + 2)) / 3.0) / GiB : 0.0;
     const double need_gb = ltab_gb + 7.5 * (fbytes(prefix + ".bwt") + fbytes(prefix + ".rbwt")) / GiB +
-                           n_lanes * (std::min(fixed, 2.0 * fixed * grp) + per_gib * grp) + 1.7 * grp +
-                           (n_lanes + 3) * 0.8 * grp + 2.0;
+                           n_lanes * (std::min(fixed, 2.0 * fixed * grp) + per_gib * grp) + ingest_gb + 2.0;
     const char *ag = getenv("IBWA_ARENA_GB");
     std::vector<std::thread> th;
     std::vector<int> rc(n_used, 0);
@@ -503,23 +591,34 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
   ph.mark("device arena");  // HIP start-up, and the wait for memory a previous process released
   // FASTQ parsed on the GPUs: n_lanes + 3 ingest contexts per GPU (their own streams and buffers;
   // ingest.h's slots); the first region is read and parsed while the index loads
-  std::vector<ibwa_ctx_t *> ing;
-  std::unique_ptr<FastqGpu> fg;
+  std::vector<std::vector<ibwa_ctx_t *>> ings(n_in);
+  std::vector<std::unique_ptr<FastqGpu>> fgs(n_in);
   struct Destroy {
-    std::vector<ibwa_ctx_t *> &v;
-    std::unique_ptr<FastqGpu> &f;
+    std::vector<std::vector<ibwa_ctx_t *>> &v;
+    std::vector<std::unique_ptr<FastqGpu>> &f;
     ~Destroy() {
-      f.reset();
-      for (auto *x : v) ibwa_ctx_destroy(x);
+      for (auto &x : f) x.reset();
+      for (auto &w : v)
+        for (auto *x : w) ibwa_ctx_destroy(x);
     }
-  } destroy_ing{ing, fg};
-  if (fq_dev) {
+  } destroy_ing{ings, fgs};
+  for (int i = 0; i < n_in; ++i) {
+    const char *fq_dev = ins[i].fq_dev;
+    if (!fq_dev) continue;
+    std::vector<ibwa_ctx_t *> &ing = ings[i];
+    std::unique_ptr<FastqGpu> &fg = fgs[i];
     // one slot per group a lane can hold and the group being launched, and two more parsed ahead:
     // a parse waits for launch boundaries of the searches (their grids hold every CU), so with one
     // slot ahead the launching thread still waited (6.9 s of waits at 50 M reads, r04_e2e_50m_v2)
     // (the producer parses one region at a time, so a GPU's slots share one parse scratch: only the
     // kept reads stay per slot)
-    const int n_slots = n_lanes + 3;
+    // Pair mode: each input has its own producer thread, so each has its own scratch -- a shared
+    // one would need the two producers' parses serialised (ibwa_fq_share_scratch), and a region of
+    // one input would wait behind the other's; 1.7x a piece per input is small next to the lanes'
+    // share of the arena.  The lanes are shared, so one region fewer is parsed ahead per input: a
+    // slot per group the lanes can hold (all of them, once the other input has ended), the group
+    // being launched, and one ahead -- two regions ahead for the two inputs together, as before.
+    const int n_slots = n_lanes + (pair ? 2 : 3);
     for (int sl = 0; sl < n_slots; ++sl)
       for (int g = 0; g < n_gpus; ++g) {
         ibwa_ctx_t *x = nullptr;
@@ -566,52 +665,55 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
       return die("replicate index");
     }
   }
-  fwrite(&opt, sizeof opt, 1, out);  // bwtaln.c:192
+  for (int i = 0; i < n_in; ++i) fwrite(&ins[i].opt, sizeof ins[i].opt, 1, outs[i]);  // bwtaln.c:192
   ph.mark("load index");
 
   // the index's device structures for these options are built while the first reads are parsed
   std::vector<int> prep_rc(n_gpus, 0);
   std::vector<std::thread> prep;
   for (int g = 0; g < n_gpus; ++g) prep.emplace_back([&, g]() { prep_rc[g] = ibwa_ctx_prepare(ctx[g], &opt); });
-  Group cur;
-  Batch sub, carry;
-  bool has_carry = false;
-  bool eof = false;
-  double parse_s = 0;  // wall time of the FASTQ parse (all host threads, or waiting for the GPUs')
-  bool dev_active = fg != nullptr, dev_done = false;
-  auto timed_read = [&](Group &into) {
+  // an input's reading state: its next group, the host readers' carry between groups, its counters
+  struct InState {
+    Group cur;
+    int have = 0;  // what the last read gave: 1 a group (cur), 0 the end of the input, -1 bad input
+    Batch sub, carry;
+    bool has_carry = false;
+    bool eof = false;
+    double parse_s = 0;  // wall time of the FASTQ parse (all host threads, or waiting for the GPUs')
+    bool dev_active = false, dev_done = false;
+    int64_t tot_seqs = 0;
+  };
+  std::vector<InState> st(n_in);
+  for (int i = 0; i < n_in; ++i) st[i].dev_active = fgs[i] != nullptr;
+  auto timed_read = [&](int i) {
+    InState &s = st[i];
+    Group &into = s.cur;
+    FastqGpu *fg = fgs[i].get();
     const auto t = std::chrono::steady_clock::now();
     int r = 0;
     into.dev = false;
-    if (dev_active) {
+    if (s.dev_active) {
       if (fg->next(into.dg)) {
         into.dev = true;
         r = 1;
       } else {
-        dev_active = false;
+        s.dev_active = false;
         if (fg->handoff()) {  // the host readers from the first batch the device path did not take
-          fprintf(stderr, "[ibwa-amd aln] the host readers take over at byte %llu\n",
-                  (unsigned long long)fg->handoff_offset());
-          if (!rd.in.seek(fg->handoff_offset())) r = -1;
+          fprintf(stderr, "[ibwa-amd aln] the host readers take over at byte %llu%s\n",
+                  (unsigned long long)fg->handoff_offset(), tag(i));
+          if (!ins[i].rd->in.seek(fg->handoff_offset())) r = -1;
         } else {
-          dev_done = true;  // the input ended on the GPU path
+          s.dev_done = true;  // the input ended on the GPU path
         }
       }
     }
-    if (!into.dev && r == 0 && !dev_done) r = read_group(rd, fb, opt, into.b, sub, carry, has_carry, &eof);
-    parse_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    return r;
+    if (!into.dev && r == 0 && !s.dev_done)
+      r = read_group(*ins[i].rd, ins[i].fb, ins[i].opt, into.b, s.sub, s.carry, s.has_carry, &s.eof);
+    s.parse_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+    return s.have = r;
   };
-  int64_t tot_seqs = 0;
-  std::thread writer;
   std::atomic<bool> write_failed{false};
-  struct JoinAtExit {  // an early return still waits for the write in flight
-    std::thread &t;
-    ~JoinAtExit() {
-      if (t.joinable()) t.join();
-    }
-  } join_writer{writer};
-  int have = timed_read(cur);
+  for (int i = 0; i < n_in; ++i) timed_read(i);
   for (auto &t : prep) t.join();
   for (int g = 0; g < n_gpus; ++g)
     if (prep_rc[g]) return die("prepare the index");
@@ -662,8 +764,19 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     }
     return b;
   };
+  // one ordered writer per output: a group's write overlaps the next groups' alignment, and a write
+  // to one output never waits for the other's
+  std::vector<std::thread> writers(n_in);
+  struct JoinAtExit {  // an early return still waits for the writes in flight
+    std::vector<std::thread> &v;
+    ~JoinAtExit() {
+      for (auto &t : v)
+        if (t.joinable()) t.join();
+    }
+  } join_writers{writers};
   struct Job {
     Group b;
+    int in = 0;  // the input the group belongs to
     std::vector<SaiBuf> sai;
     std::vector<int> rc;
     std::vector<std::thread> th;
@@ -694,11 +807,14 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     if (J.b.dev)
       for (int g = 0; g < n_gpus; ++g) {
         const auto s0 = std::chrono::steady_clock::now();
-        J.rc[g] = ibwa_batch_stage_fq(cx[g], fg->ctx_of(J.b.dg, g), J.b.dg.first[g], J.b.dg.count[g], J.b.dg.max_len);
+        J.rc[g] = ibwa_batch_stage_fq(cx[g], fgs[J.in]->ctx_of(J.b.dg, g), J.b.dg.first[g], J.b.dg.count[g],
+                                      J.b.dg.max_len);
         stage_ms[g] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
       }
+    const ibwa_gap_opt_t &opt = ins[J.in].opt;
+    const char *in_tag = tag(J.in);
     for (int g = 0; g < n_gpus; ++g) {
-      J.th.emplace_back([&J, &cx, &opt, &take_buf, g, n, per, sms = stage_ms[g]]() {
+      J.th.emplace_back([&J, &cx, &opt, &take_buf, in_tag, g, n, per, sms = stage_ms[g]]() {
         const Group &cur = J.b;
         int64_t b = std::min<int64_t>(n, g * per), e = std::min<int64_t>(n, b + per);
         if (cur.dev) b = 0, e = cur.dg.count[g];
@@ -741,8 +857,8 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
           };
           ibwa_run_stats_t st;
           ibwa_batch_stats(cx[g], &st);
-          fprintf(stderr, "[ibwa-amd aln] slice %d: %lld reads, stage %.1f run %.1f (of which allocating %.1f) fetch %.1f ms\n",
-                  g, (long long)(e - b), ms(c0, c1) + sms, ms(c1, c2), st.ms_alloc, ms(c2, c3));
+          fprintf(stderr, "[ibwa-amd aln] slice %d: %lld reads, stage %.1f run %.1f (of which allocating %.1f) fetch %.1f ms%s\n",
+                  g, (long long)(e - b), ms(c0, c1) + sms, ms(c1, c2), st.ms_alloc, ms(c2, c3), in_tag);
         }
       });
     }
@@ -753,9 +869,12 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     for (auto &t : J.th) t.join();
     J.th.clear();
     J.active = false;
-    if (J.b.dev) fg->release(J.b.dg);  // its ingest slot may be parsed over
+    if (J.b.dev) fgs[J.in]->release(J.b.dg);  // its ingest slot may be parsed over
     for (int g = 0; g < n_gpus; ++g)
       if (J.rc[g]) return die("aln");
+    std::thread &writer = writers[J.in];
+    FILE *out = outs[J.in];
+    int64_t &tot_seqs = st[J.in].tot_seqs;
     tot_seqs += J.b.n();
     fprintf(stderr, "[bwa_aln_core] calculate SA coordinate... %.2f sec\n",
             std::chrono::duration<double>(std::chrono::steady_clock::now() - J.t0).count());
@@ -773,45 +892,61 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
       }
     });
     fprintf(stderr, "0.00 sec\n");
-    fprintf(stderr, "[bwa_aln_core] %lld sequences have been processed.\n", (long long)tot_seqs);
+    fprintf(stderr, "[bwa_aln_core] %lld sequences have been processed.%s\n", (long long)tot_seqs, tag(J.in));
     return 0;
   };
   int64_t k = 0;  // groups launched
   // IBWA_ALN_PARSE_ONLY=1 (measurement): the input is read and parsed into groups, nothing is aligned
   const bool parse_only = env_int("IBWA_ALN_PARSE_ONLY", 0) != 0;
   const auto t_parse_only = std::chrono::steady_clock::now();
-  while (have > 0 && parse_only) {
-    tot_seqs += cur.n();
-    if (cur.dev) fg->release(cur.dg);
-    have = timed_read(cur);
+  for (int i = 0; i < n_in && parse_only; ++i) {
+    InState &s = st[i];
+    while (s.have > 0) {
+      s.tot_seqs += s.cur.n();
+      if (s.cur.dev) fgs[i]->release(s.cur.dg);
+      timed_read(i);
+    }
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_parse_only).count();
+    fprintf(stderr, "[ibwa-amd aln] parse only: %lld reads, %.3f s parsing (%.3f s after the first group) = %.2f M reads/s (%s)%s\n",
+            (long long)s.tot_seqs, s.parse_s, dt, s.tot_seqs / std::max(s.parse_s, 1e-9) / 1e6,
+            fgs[i] ? "GPU parse" : "host parse", tag(i));
   }
-  if (parse_only) {
-    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_parse_only).count();
-    fprintf(stderr, "[ibwa-amd aln] parse only: %lld reads, %.3f s parsing (%.3f s after the first group) = %.2f M reads/s (%s)\n",
-            (long long)tot_seqs, parse_s, s, tot_seqs / std::max(parse_s, 1e-9) / 1e6, fg ? "GPU parse" : "host parse");
-  }
-  while (have > 0) {
+  // Groups go to the lanes in one FIFO.  While both inputs of a pair have groups they take turns;
+  // when one has ended the other takes every lane.  A bad input ends the run as it does alone: the
+  // groups in flight are finished and written, and the exit code says so.
+  bool bad_input = false;
+  for (int turn = 0; !bad_input;) {
+    int i = -1;
+    for (int d = 0; d < n_in && i < 0; ++d)
+      if (st[(turn + d) % n_in].have > 0) i = (turn + d) % n_in;
+    if (i < 0) break;
+    InState &s = st[i];
     Job &J = jobs[k % n_lanes];
     if (J.active)  // the oldest group in flight
       if (int rc = finish(J)) return rc;
     if (opt.trim_qual >= 1)  // once per 0x40000-read batch, as bwa_read_seq (bwaseqio.c:206)
-      for (const auto &t : cur.trims())
+      for (const auto &t : s.cur.trims())
         if (t.second) fprintf(stderr, "[bwa_read_seq] %.1f%% bases are trimmed.\n", 100.0f * t.first / t.second);
-    std::swap(J.b, cur);
+    std::swap(J.b, s.cur);
+    J.in = i;
     launch(J, lctx[k % n_lanes]);
     ++k;
-    have = timed_read(cur);  // the next group is parsed while the GPUs work
+    bad_input = timed_read(i) < 0;  // the next group is parsed while the GPUs work
+    turn = (i + 1) % n_in;
   }
+  for (int i = 0; i < n_in; ++i) bad_input = bad_input || st[i].have < 0;
   for (int64_t q = std::max<int64_t>(0, k - n_lanes); q < k; ++q)
     if (jobs[q % n_lanes].active)
       if (int rc = finish(jobs[q % n_lanes])) return rc;
   ph.mark("align (groups overlapped, next group parsed meanwhile)");
-  if (writer.joinable()) writer.join();
+  for (auto &w : writers)
+    if (w.joinable()) w.join();
   if (write_failed) {
     fprintf(stderr, "[ibwa-amd aln] write failed\n");
     return 1;
   }
-  if (out != stdout) fclose(out);
+  for (FILE *out : outs)  // both outputs of a pair are complete on disk before the process ends
+    if (out != stdout) fclose(out);
   ph.mark("last records written");
   int64_t dev_now = 0, dev_peak = 0;
   ibwa_device_bytes(&dev_now, &dev_peak);
@@ -823,22 +958,28 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
     if (ibwa_arena_stats(d, &asz, &aused, &apeak) == 0 && asz)
       fprintf(stderr, "[ibwa-amd aln] arena on GPU %d: %.1f GB, peak use %.1f GB\n", d, asz / 1e9, apeak / 1e9);
   }
-  if (fg) {
-    fprintf(stderr, "[ibwa-amd aln] input parsed on the GPUs: %lld records, %.2f s parsing ahead of the alignment (%.0f ms "
-                    "of device time: H2D copies + kernels)%s\n",
-            (long long)fg->records(), fg->parse_s(), fg->dev_ms(), fg->handoff() ? "; the host readers took the rest" : "");
-    if (fg->gzip())
-      fprintf(stderr, "[ibwa-amd aln] %s input inflated on %d host threads: %.3f GB in %.2f s of the reader thread "
-                      "(ahead of the parse)\n",
-              fg->bgzf() ? "BGZF" : "gzip", ibwa_cli::gz_threads(), fg->input_bytes() / 1e9, fg->inflate_s());
-  }
-  if (parse_s > 0 && fg && !fg->handoff()) {  // every record parsed on the GPUs: the time is waiting
-    fprintf(stderr, "[ibwa-amd aln] input: %lld reads parsed on the GPUs, %.2f s waited for parsed groups\n",
-            (long long)tot_seqs, parse_s);
-  } else if (parse_s > 0) {
-    const int nt = fb ? ibwa_sam::host_threads() : 1;
-    fprintf(stderr, "[ibwa-amd aln] input parse: %lld reads in %.2f s on %d host threads = %.2f M reads/s (%.3f M per thread)\n",
-            (long long)tot_seqs, parse_s, nt, tot_seqs / parse_s / 1e6, tot_seqs / parse_s / 1e6 / nt);
+  for (int i = 0; i < n_in; ++i) {  // the totals of each input
+    const FastqGpu *fg = fgs[i].get();
+    const double parse_s = st[i].parse_s;
+    const int64_t tot_seqs = st[i].tot_seqs;
+    if (fg) {
+      fprintf(stderr, "[ibwa-amd aln] input parsed on the GPUs: %lld records, %.2f s parsing ahead of the alignment (%.0f ms "
+                      "of device time: H2D copies + kernels)%s%s\n",
+              (long long)fg->records(), fg->parse_s(), fg->dev_ms(), fg->handoff() ? "; the host readers took the rest" : "",
+              tag(i));
+      if (fg->gzip())
+        fprintf(stderr, "[ibwa-amd aln] %s input inflated on %d host threads: %.3f GB in %.2f s of the reader thread "
+                        "(ahead of the parse)%s\n",
+                fg->bgzf() ? "BGZF" : "gzip", ibwa_cli::gz_threads(), fg->input_bytes() / 1e9, fg->inflate_s(), tag(i));
+    }
+    if (parse_s > 0 && fg && !fg->handoff()) {  // every record parsed on the GPUs: the time is waiting
+      fprintf(stderr, "[ibwa-amd aln] input: %lld reads parsed on the GPUs, %.2f s waited for parsed groups%s\n",
+              (long long)tot_seqs, parse_s, tag(i));
+    } else if (parse_s > 0) {
+      const int nt = ins[i].fb ? ibwa_sam::host_threads() : 1;
+      fprintf(stderr, "[ibwa-amd aln] input parse: %lld reads in %.2f s on %d host threads = %.2f M reads/s (%.3f M per thread)%s\n",
+              (long long)tot_seqs, parse_s, nt, tot_seqs / parse_s / 1e6, tot_seqs / parse_s / 1e6 / nt, tag(i));
+    }
   }
   // Every record is written and every kernel has finished: the process ends here.  Tearing down the
   // contexts, the ingest slots and the pinned buffers one by one only hands back what the driver and
@@ -849,10 +990,10 @@ int run_aln(Reader &rd, FastqBulk *fb, const ibwa_gap_opt_t &opt, const std::str
               std::chrono::duration<double>(std::chrono::steady_clock::now() - g_proc_t0).count());
     fflush(stdout);
     fflush(stderr);
-    _exit(have < 0 ? 1 : 0);
+    _exit(bad_input ? 1 : 0);
   }
   for (int l = n_lanes - 1; l >= 1; --l)  // lanes sharing the index first
     for (auto *x : lctx[l]) ibwa_ctx_destroy(x);
   for (auto *x : ctx) ibwa_ctx_destroy(x);
-  return have < 0 ? 1 : 0;
+  return bad_input ? 1 : 0;
 }

@@ -14,16 +14,18 @@ namespace {
 std::mutex g_getopt_lock;  // getopt keeps global state
 }
 
-extern "C" int ibwa_aln_parse_args(int argc, char *const *argv, ibwa_gap_opt_t *opt, int *n_gpus, const char **fn_out) {
+extern "C" int ibwa_aln_parse_args2(int argc, char *const *argv, ibwa_gap_opt_t *opt, int *n_gpus, const char **fn_out,
+                                    const char **fn_out2) {
   std::lock_guard<std::mutex> lk(g_getopt_lock);
   ibwa_gap_init_opt(opt);  // gap_init_opt (bwtaln.c:21-37)
   if (n_gpus) *n_gpus = 1;
   if (fn_out) *fn_out = nullptr;
+  if (fn_out2) *fn_out2 = nullptr;
   int opte = -1, c;
   optind = 0;  // full re-initialisation (GNU getopt), so the parser can be called again
   opterr = 1;
-  // bwtaln.c:249-284, plus -G (number of GPUs)
-  while ((c = getopt(argc, argv, "n:o:e:i:d:l:k:cLR:m:t:NM:O:E:q:f:b012IB:G:")) >= 0) {
+  // bwtaln.c:249-284, plus -G (number of GPUs) and -F (the second end's output: pair mode)
+  while ((c = getopt(argc, argv, "n:o:e:i:d:l:k:cLR:m:t:NM:O:E:q:f:b012IB:G:F:")) >= 0) {
     switch (c) {
       case 'n':
         if (strstr(optarg, ".")) opt->fnr = (float)atof(optarg), opt->max_diff = -1;
@@ -53,6 +55,7 @@ extern "C" int ibwa_aln_parse_args(int argc, char *const *argv, ibwa_gap_opt_t *
       case 'I': opt->mode |= IBWA_MODE_IL13; break;
       case 'B': opt->mode |= atoi(optarg) << 24; break;
       case 'G': if (n_gpus) *n_gpus = atoi(optarg); break;
+      case 'F': if (fn_out2) *fn_out2 = optarg; break;
       default: return -1;
     }
   }
@@ -61,4 +64,8 @@ extern "C" int ibwa_aln_parse_args(int argc, char *const *argv, ibwa_gap_opt_t *
     opt->mode &= ~IBWA_MODE_GAPE;
   }
   return optind;
+}
+
+extern "C" int ibwa_aln_parse_args(int argc, char *const *argv, ibwa_gap_opt_t *opt, int *n_gpus, const char **fn_out) {
+  return ibwa_aln_parse_args2(argc, argv, opt, n_gpus, fn_out, nullptr);
 }

@@ -106,6 +106,8 @@ CAPI = {
     "ibwa_batch_stats": (_i, [_vp, c.POINTER(RunStats)]),
     "ibwa_ctx_set_tuning": (_i, [_vp, _i, _i, _i]),
     "ibwa_aln_parse_args": (_i, [_i, c.POINTER(c.c_char_p), c.POINTER(GapOpt), c.POINTER(_i), c.POINTER(c.c_char_p)]),
+    "ibwa_aln_parse_args2": (_i, [_i, c.POINTER(c.c_char_p), c.POINTER(GapOpt), c.POINTER(_i), c.POINTER(c.c_char_p),
+                                  c.POINTER(c.c_char_p)]),
     "ibwa_batch_retry_info": (_i, [_vp, _vp, _vp, _i64, c.POINTER(_i64)]),
     "ibwa_batch_diag": (_i, [_vp, _i, _vp, _u64]),
     "ibwa_ctx_set_option": (_i, [_vp, c.c_char_p, c.c_long]),
@@ -184,6 +186,21 @@ def parse_aln_args(args):
     if rc != len(argv):
         raise IbwaError(f"unexpected positional arguments in {args}")
     return o
+
+
+def parse_aln_cmdline(args):
+    """A whole `aln` command line (ibwa_aln_parse_args2: options, -G, -f, and -F of the pair mode)
+    -> (GapOpt, n_gpus, fn_out, fn_out2, first_positional); the paths are None when not given and
+    first_positional indexes `args` (len(args) when there is no positional argument; options come
+    before the positional arguments, as on the CLI)."""
+    argv = [b"aln"] + [a.encode() for a in args]
+    arr = (c.c_char_p * len(argv))(*argv)
+    o, n_gpus, f1, f2 = GapOpt(), _i(1), c.c_char_p(), c.c_char_p()
+    rc = lib().ibwa_aln_parse_args2(len(argv), arr, c.byref(o), c.byref(n_gpus), c.byref(f1), c.byref(f2))
+    if rc < 0:
+        raise IbwaError(f"bad aln options {args}")
+    paths = [p.value.decode() if p.value is not None else None for p in (f1, f2)]
+    return o, n_gpus.value, paths[0], paths[1], rc - 1
 
 
 def read_bwt_file(path):

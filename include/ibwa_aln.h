@@ -285,6 +285,15 @@ const char *ibwa_build_id(void);
  * unknown option.  n_gpus / fn_out (-f) may be NULL.  Thread-safe (getopt is serialised).
  */
 int ibwa_aln_parse_args(int argc, char *const *argv, ibwa_gap_opt_t *opt, int *n_gpus, const char **fn_out);
+/*
+ * ibwa_aln_parse_args plus -F FILE, the CLI's pair mode (`aln -f out1.sai -F out2.sai <prefix>
+ * <in1.fq> <in2.fq>`: both ends of a pair aligned by one process, one .sai each).  *fn_out2 = -F's
+ * argument, NULL when the option is absent; fn_out2 may be NULL (the option is then parsed and
+ * dropped, as -f is with fn_out NULL -- which is what ibwa_aln_parse_args does).  No reference
+ * counterpart: like -G, the letter is free in bwa_aln's option string (bwtaln.c:249).
+ */
+int ibwa_aln_parse_args2(int argc, char *const *argv, ibwa_gap_opt_t *opt, int *n_gpus, const char **fn_out,
+                         const char **fn_out2);
 
 /*
  * Reads of the last ibwa_batch_run that the first pass handed on, and the pass that resolved

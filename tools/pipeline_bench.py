@@ -9,7 +9,11 @@ user runs it (files in, files out, wall clock per command).  The reference's own
 timed on a bounded sample of the same pairs with the same index files, and the SAM both write for
 that sample is compared line by line (except @PG).
 
-usage: tools/pipeline_bench.py [--scale 0.1] [--pairs 1000000] [--sample 20000] [--out json]
+The two ends' `aln` is timed as two processes at once, as two processes one after the other and,
+with --pair-mode, as one process writing both .sai files (`aln -f out1 -F out2`, `aln_pair_mode` in
+the result: wall, phase table, memory, .sai compared with the sequential runs').
+
+usage: tools/pipeline_bench.py [--scale 0.1] [--pairs 1000000] [--sample 20000] [--pair-mode] [--out json]
 """
 import argparse
 import gzip  # noqa: F401  (kept for ad-hoc inspection of outputs)
@@ -40,9 +44,9 @@ def log(*a):
 LAST_ERR = [""]
 
 
-def run(argv, stdout=None, timeout=1200):
+def run(argv, stdout=None, timeout=1200, env=None):
     t = time.perf_counter()
-    r = subprocess.run(argv, stdout=stdout, stderr=subprocess.PIPE, timeout=timeout)
+    r = subprocess.run(argv, stdout=stdout, stderr=subprocess.PIPE, timeout=timeout, env=env)
     dt = time.perf_counter() - t
     LAST_ERR[0] = r.stderr.decode(errors="replace")
     if r.returncode != 0:
@@ -141,6 +145,31 @@ def load_s(err):
     return None
 
 
+def aln_phases(err):
+    """`aln`'s phase table (its "wall s:" line: phase names, each followed by its seconds) as a dict,
+    and how many such lines there were (one per process)."""
+    import re
+    lines = [ln.split("wall s:", 1)[1] for ln in err.splitlines() if ln.startswith("[ibwa-amd aln] wall s:")]
+    ph = {}
+    for ln in lines:
+        for name, s in re.findall(r" (.+?) (\d+\.\d\d)(?= |$)", ln):
+            ph[name] = ph.get(name, 0.0) + float(s)
+    return ph, len(lines)
+
+
+def aln_memory(err):
+    """The arena's size and peak use, and the engine buffers' peak (GB), from `aln`'s closing lines."""
+    import re
+    m = {}
+    a = re.search(r"arena on GPU 0: ([\d.]+) GB, peak use ([\d.]+) GB", err)
+    if a:
+        m["arena_gb"], m["arena_peak_gb"] = float(a.group(1)), float(a.group(2))
+    p = re.search(r"device memory: peak ([\d.]+) GB", err)
+    if p:
+        m["engine_peak_gb"] = float(p.group(1))
+    return m
+
+
 def file_digest(path):
     import hashlib
     h = hashlib.sha1()
@@ -167,6 +196,9 @@ def main():
     ap.add_argument("--concurrent-lanes", default="1,2",
                     help="IBWA_ALN_LANES of each of the two processes aligning the ends at once (the first is "
                          "the pipeline's: one lane each, the other process overlapping it; then the others)")
+    ap.add_argument("--pair-mode", action="store_true",
+                    help="also align the two ends in one process (aln -f out1 -F out2 <prefix> <in1> <in2>), "
+                         "after the sequential runs its .sai files are compared with")
     ap.add_argument("--sampe-workers", default="1,2", help="sampe -R -G values to time (the first is sampe_s)")
     ap.add_argument("--out", default="")
     ap.add_argument("--diag", action="store_true", help="only run `aln` on the sample's end 2 with IBWA_VERBOSE")
@@ -226,7 +258,29 @@ def main():
                      "sai_equal_first": [open(f_, "rb").read() for f_ in csai] == csai_first})
             log(f"ibwa-amd: both ends' aln at once, {lanes} lane(s) per process: {pair_s:.2f} s for the pair")
     time.sleep(8.0)  # their memory wiped before the sequential runs
-    res["aln_s"] = [run([CLI, "aln", "-f", sai[e], P, fq[e]]) for e in (0, 1)]
+    res["aln_s"], seq_err = [], []
+    for e in (0, 1):
+        res["aln_s"].append(run([CLI, "aln", "-f", sai[e], P, fq[e]]))
+        seq_err.append(LAST_ERR[0])
+    if a.pair_mode:
+        # the one-process form on the same two files: one arena, one index load, the lanes shared
+        psai = [os.path.join(tmp, f"p{e}.sai") for e in (1, 2)]
+        time.sleep(8.0)  # the sequential runs' memory wiped first, as before every other leg
+        pair_s = run([CLI, "aln", "-f", psai[0], "-F", psai[1], P, fq[0], fq[1]], env=dict(os.environ, IBWA_ALN_TIMES="1"))
+        ph, n_tables = aln_phases(LAST_ERR[0])
+        same = [file_digest(psai[e]) == file_digest(sai[e]) for e in (0, 1)]
+        ph1, _ = aln_phases(seq_err[0])
+        res["aln_pair_mode"] = {
+            "wall_s": pair_s, "phases_s": ph, "phase_tables": n_tables, "sai_equal_sequential": same,
+            "one_end_wall_s": res["aln_s"][0], "pair_over_one_end": pair_s / res["aln_s"][0],
+            "sequential_ends_wall_s": sum(res["aln_s"]), "memory": aln_memory(LAST_ERR[0]),
+            "one_end": {"phases_s": ph1, "memory": aln_memory(seq_err[0])}}
+        if a.concurrent_ends:
+            res["aln_pair_mode"]["concurrent_processes_wall_s"] = res["aln_concurrent"]["pair_wall_s"]
+        log(f"ibwa-amd: both ends in one aln process: {pair_s:.2f} s = {pair_s / res['aln_s'][0]:.2f} x one end "
+            f"(sequential ends {sum(res['aln_s']):.2f} s); .sai equal the sequential runs' {same}")
+        for f_ in psai:
+            os.unlink(f_)
     if a.concurrent_ends:
         same = all(open(csai[e], "rb").read() == open(sai[e], "rb").read() for e in (0, 1))
         c = res["aln_concurrent"]
