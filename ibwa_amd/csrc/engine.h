@@ -119,6 +119,11 @@ struct GapArgs {
   // depth) and expanded from one 32 B load of its children's intervals instead of two Occ blocks.
   const uint2 *ltab[2];
   uint32_t tab_k;            // 0: off (resume states leave with intervals: the cooperative pass has no tables)
+  // Tail jump: such a node's exact tail (bwtgap.c:160-163) takes its steps down to depth tab_k + 1 from
+  // one 8 B table entry (its string followed by the read's next symbols) instead of one Occ round trip
+  // each.  tail_jumps: optional, the launch adds the jumps it took.
+  uint32_t tail_tab;         // 0: every tail step from Occ blocks
+  unsigned long long *tail_jumps;
   AlnOpt o;
 };
 constexpr uint32_t LTAB_MARK = 0xFFFFFF00u;  // y >= this: a node stored by its string (no l can be: seq_len < it)

@@ -299,6 +299,7 @@ struct ibwa_ctx {
   int jump_derive = 1;        // option: derive them for a loaded index when HBM allows
   int exact_jump = 1;
   int width_tab = 1;           // option: k_width's first steps from the level tables (first pass)
+  int gap_tail_tab = 1;        // option: exact tails of nodes stored by their strings jump by the level tables
   int width_jump = 1;         // option: k_width steps one-row intervals from the text (2: derive SA / text for it)
   uint32_t sa_intv = 0;
   bool sa_loaded[2] = {false, false};  // sa_s[s] holds a sampled SA of the resident index
@@ -764,6 +765,7 @@ int ibwa_ctx_set_option(ibwa_ctx_t *c, const char *key, long value) {
   else if (k == "jump_derive") c->jump_derive = value != 0;
   else if (k == "width_jump" && value >= 0 && value <= 2) c->width_jump = (int)value;
   else if (k == "width_tab" && (value == 0 || value == 1)) c->width_tab = (int)value;
+  else if (k == "gap_tail_tab" && (value == 0 || value == 1)) c->gap_tail_tab = (int)value;
   else if (k == "diag") c->diag = value != 0;
   else if (k == "sa_walk") c->sa_walk = value != 0;
   else if (k == "gap_coop") c->gap_coop = value != 0;
@@ -902,6 +904,7 @@ int ibwa_ctx_share_index(ibwa_ctx_t *dst, const ibwa_ctx_t *src) {
   dst->exact_jump = src->exact_jump;
   dst->width_jump = src->width_jump;
   dst->width_tab = src->width_tab;
+  dst->gap_tail_tab = src->gap_tail_tab;
   dst->share_src = const_cast<ibwa_ctx *>(src);
   ++dst->share_src->n_borrowers;
   return 0;
@@ -1468,6 +1471,7 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
   c->stats.resume_records = 0;
   c->stats.resume_records_peak = c->stats.resume_records_cap = 0;
   c->stats.coop_pages_peak = c->stats.coop_pages_cap = 0;
+  c->stats.n_tail_jumps = 0;
   if (v2) {
     if (int rc = ensure_kmer(c)) return rc;
     c->stats.path = 2;
@@ -1563,6 +1567,7 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
     if (int rc = c->d_status.ensure(std::max<int64_t>(n, 1) * 4)) return rc;
     if (int rc = c->d_counter.ensure(64)) return rc;
     HIPCHK(zero_async(c->d_counter.as<unsigned long long>() + 1, 8, c->stream));
+    HIPCHK(zero_async(c->d_counter.as<unsigned long long>() + 7, 8, c->stream));  // GapArgs::tail_jumps
     // The reads of chunk [b0, b0 + cnt) that left a resume state go through the cooperative pass right
     // after their chunk's first pass, so the state buffer holds one chunk's states at a time: a read
     // it resolves is done (status 0), one it hands on starts over in the passes below.
@@ -1739,6 +1744,8 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
         G.ltab[0] = c->ltab[0].as<uint2>();
         G.ltab[1] = c->ltab[1].as<uint2>();
         G.tab_k = (uint32_t)c->ltab_K;
+        G.tail_tab = (uint32_t)c->gap_tail_tab;
+        G.tail_jumps = c->d_counter.as<unsigned long long>() + 7;
       }
       G.cap1 = P0r;
       G.hit_slots = std::min<uint32_t>(c->gap_hit_slots, P0r / 2);
@@ -1802,7 +1809,7 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
                 it[(size_t)(cnt * 0.99)], it[(size_t)(cnt * 0.9999)], mx, b, sum / (b * 1e-3));
       }
       if (c->prof_phases) {
-        unsigned long long pf[19];
+        unsigned long long pf[23];
         HIPCHK(hipMemcpy(pf, c->d_prof.p, sizeof pf, hipMemcpyDeviceToHost));
         const char *nm[4] = {"claim", "pop", "wait", "rest"};
         double tot = (double)(pf[0] + pf[1] + pf[2] + pf[3]);
@@ -1816,6 +1823,9 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
         fprintf(stderr, "[ibwa_amd] k_gapped loads per live lane-iteration: block %.3f second block %.3f widths %.3f "
                 "seed widths %.3f candidate %.3f; exact steps %.3f (unique interval %.3f) (%.3g live lane-iterations)\n",
                 pf[11] / li, pf[12] / li, pf[13] / li, pf[14] / li, pf[15] / li, pf[17] / li, pf[18] / li, (double)pf[16]);
+        fprintf(stderr, "[ibwa_amd] k_gapped tail jumps: %.2f per read (%.2f onto an empty entry), %.2f symbols per "
+                "read; pure-match run steps %.3f per live lane-iteration (%llu)\n", (double)pf[19] / cnt,
+                (double)pf[20] / cnt, (double)pf[21] / cnt, pf[22] / li, pf[22]);
       }
       if (resume_states)
         if (int rc = coop_resumed(b0, cnt)) return rc;
@@ -2314,6 +2324,9 @@ int ibwa_batch_run(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int batch_max_len) 
                           c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->stream_len = std::min<unsigned long long>(c->stream_len, c->stream_total);
+    unsigned long long tj = 0;
+    HIPCHK(hipMemcpy(&tj, c->d_counter.as<unsigned long long>() + 7, 8, hipMemcpyDeviceToHost));
+    c->stats.n_tail_jumps = (int64_t)tj;
   }
   c->stats.ms_retry = ms_r + res_ms;
   c->stats.n_retry = (int64_t)c->retry_ids.size() + res_ok;

@@ -194,7 +194,9 @@ size_t gapped_lds_bytes(int n_stacks, int block, bool wide, int max_pages, int p
 // PROF: per-wave cycle accounting of the loop's phases into A.prof[] (diagnostics build of
 // the same kernel): 0 claim, 1 pop, 2 wait for the loads, 3 rest; then wave-level event
 // counts (the wave executes a block once for all its lanes in it): 4 exact steps, 5 push-loop
-// trips, 6 hit blocks, 7 read ends, 8 expansions, 9 wave iterations, 10 read claims.
+// trips, 6 hit blocks, 7 read ends, 8 expansions, 9 wave iterations, 10 read claims; then lane
+// counts: 11-18 the loads, 19 tail jumps, 20 jumps onto an empty entry, 21 symbols the jumps took,
+// 22 pure-match run steps.
 template <bool WIDE, bool PROF, bool LW, int NBL>
 __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long *counter) {
   static_assert(!(WIDE && LW), "the LDS-width variant is a first-pass kernel");
@@ -284,6 +286,10 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
   // so short that a hit could come at such a depth does not use them
   const uint32_t TK = LW ? A.tab_k : 0u;
   bool tabok = false;
+  // exact tails (bwtgap.c:160-163) of such nodes take their first symbols, down to depth TK + 1, from
+  // one table entry (GapArgs::tail_tab); n_tj: the wave's jumps (uniform), for GapArgs::tail_jumps
+  const bool TJ = LW && TK > 0 && A.tail_tab;
+  uint32_t n_tj = 0;
   const uint2 *W0 = nullptr, *W1 = nullptr, *SW0 = nullptr, *SW1 = nullptr;
   BMask nonempty = {0u, 0u, 0u, 0u};
   uint4 C = make_uint4(0, 0, 0, 0);
@@ -334,6 +340,11 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
   uint64_t pf8 = 0, pf9 = 0, pf10 = 0;
   // lane counts (PROF): block loads, second-block loads, width loads, seed-width loads, candidate loads, live lanes
   uint64_t pl11 = 0, pl12 = 0, pl13 = 0, pl14 = 0, pl15 = 0, pl16 = 0, pl17 = 0, pl18 = 0;
+  // tail jumps taken, jumps that landed on an empty entry, symbols they skipped; pure-match run steps:
+  // expansions of a node by its string in state M that can push only the match child, popped right
+  // after another such expansion of the lane pushed them (the round trips a run jump would remove)
+  uint64_t pl19 = 0, pl20 = 0, pl21 = 0, pl22 = 0;
+  bool pm_prev = false;  // (PROF) the lane's previous iteration was such an expansion and pushed its match child
   auto pnow = []() __attribute__((always_inline)) -> uint64_t {
     uint64_t t = 0;
     if (PROF) __asm__ volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
@@ -771,25 +782,12 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
     const uint32_t na_end = ending && !end_stat ? (uint32_t)n_aln : 0u;
     unsigned long long e_pos = 0;
     if (na_end) e_pos = atomicAdd(args()->aln_next, (unsigned long long)na_end);
-    load_blk(shd ? shp : na_end ? ent1 + (P0 - 4) : obq, (shd || na_end) ? 0u : ql, (qrun && !shq) || shd || na_end, bl);
-    load_blk(shd ? shp + 4 : obq, shd ? 0u : qk - 1, (qrun && !qkneg && !qshare && !shq) || (shd && SHW > 8), bk);
-    if (shq) {
-      const uint2 *tb = a ? A.ltab[0] : A.ltab[1];
-      const uint4 *ch = reinterpret_cast<const uint4 *>(tb + ltab_off(sdep + 1) + ((uint64_t)e.x << 2));
-      bl.v0 = ch[0];
-      bl.v1 = ch[1];
-      if (state == STATE_D) {
-        const uint2 own = tb[ltab_off(sdep) + e.x];
-        bl.v2.x = own.x;
-        bl.v2.y = own.y;
-      }
-    }
     // width bounds of strand a at positions i-2, i-1 and the seed pair
     const uint2 *Wa = a ? W1 : W0;
     const uint2 *SWa = a ? SW1 : SW0;
     // as bids (bid1 = width[i-1].bid, bid2 = width[i-2].bid), "width[i-2] == width[i-1]" (eq12), and
     // the seed pair's (sb_lo, sb_hi, seq_hi); LW: from the LDS record (bids clamped where no test
-    // can tell them apart, engine.h AlnArgs::cw)
+    // can tell them apart, engine.h AlnArgs::cw) -- no memory, so read before the loads are chosen
     uint32_t bid1 = 0, bid2 = 0, sb_lo = 0, sb_hi = 0;
     bool eq12 = false, seq_hi = false;
     const int ii = (i - 1) - (len - o.seed_len);
@@ -807,7 +805,44 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
         sb_hi = nh & 3u;
         seq_hi = (nh >> 2) & 1u;
       }
-    } else {
+    }
+    // Tail jump: a node stored by its string that takes the exact path (bwtgap.c:147, 155, 159, 160 --
+    // m, bid1, i and the state are all known here).  bwt_match_exact_alt's first tjn = min(i, TK + 1 -
+    // depth) steps from it give exactly the interval of its string followed by the read symbols
+    // str[i-1], ..., str[i-tjn], which is the level table's entry of that longer string (an empty
+    // interval at any step leaves every longer string's entry empty: k_ltab_level), so one 8 B load
+    // stands for those tjn dependent round trips.  The symbols come from the lane's 2-bit read in LDS
+    // (at most two words; position i - tjn in the low bits, as the newest symbol of a string code), so
+    // a read that may hold an N steps symbol by symbol as before.
+    const bool tj = TJ && shq && srch && i > 0 && fastrd && m == 0 && bid1 == 0 &&
+                    (state == STATE_M || (o.mode & MODE_GAPE) || e_ge == o.max_gape);
+    uint32_t tjn = 0;
+    if (LW) n_tj += (uint32_t)__popcll(__ballot(tj));
+    load_blk(shd ? shp : na_end ? ent1 + (P0 - 4) : obq, (shd || na_end) ? 0u : ql, (qrun && !shq) || shd || na_end, bl);
+    load_blk(shd ? shp + 4 : obq, shd ? 0u : qk - 1, (qrun && !qkneg && !qshare && !shq) || (shd && SHW > 8), bk);
+    if (tj) {
+      tjn = min((uint32_t)i, TK + 1u - sdep);
+      const uint32_t p0 = (uint32_t)i - tjn;
+      const uint32_t w0 = cwl[((1u + (p0 >> 4)) << nbl) + ltid], w1 = cwl[((1u + ((uint32_t)(i - 1) >> 4)) << nbl) + ltid];
+      const uint32_t fm = (1u << (2u * tjn)) - 1u;  // tjn <= 15
+      uint32_t field = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (2u * (p0 & 15u))) & fm;
+      if (a == 1 && comp) field ^= fm;
+      const uint2 *tb = a ? A.ltab[0] : A.ltab[1];
+      const uint2 iv = tb[ltab_off(sdep + tjn) + ((e.x << (2u * tjn)) | field)];
+      bl.v0.x = iv.x;
+      bl.v0.y = iv.y;
+    } else if (shq) {
+      const uint2 *tb = a ? A.ltab[0] : A.ltab[1];
+      const uint4 *ch = reinterpret_cast<const uint4 *>(tb + ltab_off(sdep + 1) + ((uint64_t)e.x << 2));
+      bl.v0 = ch[0];
+      bl.v1 = ch[1];
+      if (state == STATE_D) {
+        const uint2 own = tb[ltab_off(sdep) + e.x];
+        bl.v2.x = own.x;
+        bl.v2.y = own.y;
+      }
+    }
+    if (!LW) {
       uint2 w_im1 = make_uint2(0, 0), w_im2 = make_uint2(0, 0), sw_lo = make_uint2(0, 0), sw_hi = make_uint2(0, 0);
       if (srch && i > 0) w_im1 = Wa[i - 1];
       if (srch && i > 1) w_im2 = Wa[i - 2];
@@ -852,6 +887,10 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
         pl17 += __popcll(b17);
         pl18 += __popcll(b18);
       }
+      if (tj) {  // (per lane: every lane adds its own sums at the end)
+        ++pl19;
+        pl21 += tjn;
+      }
     }
     if (PROF) {
       __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -860,6 +899,8 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
     }
 
     // ------------------------------------------------ consume
+    const bool pm_was = PROF && pm_prev;
+    if (PROF) pm_prev = false;
     if (!fl_known) {
       fl_next = fl_ld;
       fl_known = true;
@@ -1022,11 +1063,20 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
     if (m == 0 && (state == STATE_M || (o.mode & MODE_GAPE) || e_ge == o.max_gape)) {
       // bwt_match_exact_alt over str[0..i-1] (bwtgap.c:160-163): the first step uses this
       // iteration's blocks; the rest run in sub-state 2
-      if (csym > 3) continue;
-      xk = pick4(KK, csym);
-      xl = pick4(LL, csym);
-      if (xk > xl) continue;
-      xj = i - 2;
+      if (tj) {
+        // the first tjn steps at once: the table entry of the node's string + those read symbols
+        xk = bl.v0.x;
+        xl = bl.v0.y;
+        if (PROF && xk > xl) ++pl20;
+        if (xk > xl) continue;
+        xj = i - 1 - (int)tjn;
+      } else {
+        if (csym > 3) continue;
+        xk = pick4(KK, csym);
+        xl = pick4(LL, csym);
+        if (xk > xl) continue;
+        xj = i - 2;
+      }
       xa = a;
       xe = e;
       if (xj >= 0) {
@@ -1052,6 +1102,7 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
           else if ((int)sb_lo == m_seed - 1 && (int)sb_hi == m_seed - 1 && seq_hi) allow_M = false;
         }
       }
+      if (PROF && pm_was && shq && state == STATE_M && !allow_diff) ++pl22;
       // children in the reference's push order (bwtgap.c:216-258), as bits of a mask:
       //   bit 0 insertion (open or extend), bits 1-4 deletion by A,C,G,T, bits 5-8 the
       //   mismatch / match children of symbols (str[i] + 1..4) & 3 (bit 8 = str[i] itself)
@@ -1222,6 +1273,7 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
           C_slot = slot;
           C_b = sc_base;
           C_valid = true;
+          if (PROF && shq && state == STATE_M && !allow_diff) pm_prev = true;
         }
         if (t) {
           n_free -= n_fs;
@@ -1302,10 +1354,15 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
     continue;
   }
   }
+  if (LW && lane == 0 && n_tj) {
+    KArgs *ka = args();
+    if (ka->tail_jumps) atomicAdd(ka->tail_jumps, (unsigned long long)n_tj);
+  }
   if (PROF && A.prof) {
-    const uint64_t v[19] = {pf0, pf1, pf2, pf3, pf4, pf5, pf6, pf7, pf8, pf9, pf10, pl11, pl12, pl13, pl14, pl15, pl16, pl17, pl18};
+    const uint64_t v[23] = {pf0,  pf1,  pf2,  pf3,  pf4,  pf5,  pf6,  pf7,  pf8,  pf9,  pf10, pl11,
+                            pl12, pl13, pl14, pl15, pl16, pl17, pl18, pl19, pl20, pl21, pl22};
 #pragma unroll
-    for (int q = 0; q < 19; ++q)
+    for (int q = 0; q < 23; ++q)
       if (v[q]) atomicAdd(A.prof + q, (unsigned long long)v[q]);
   }
 }

@@ -216,6 +216,8 @@ typedef struct {
 	int64_t coop_pages_peak;     /* the most bucket pages one cooperative launch took from its pool */
 	int64_t coop_pages_cap;      /* the largest launch's pool in pages (COOP_PG 16 B entries each) */
 	double ms_alloc;             /* wall time the run spent allocating device buffers (hipMalloc) */
+	int64_t n_tail_jumps;        /* exact tails the first pass started from a level-table entry
+	                                ("gap_tail_tab"; 0 when the option or the tables are off) */
 } ibwa_run_stats_t;
 int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
 
@@ -230,6 +232,10 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *                                  gapped batch too; 0: Occ steps only) -- same widths
  *   "width_tab" (0/1, default 1)   k_width takes a chain's first steps (up to gap_tab_k + 1) from
  *                                  the level tables, one round trip for all -- same widths
+ *   "gap_tail_tab" (0/1, default 1) first pass: the exact tail (bwt_match_exact_alt) of a node stored
+ *                                  by its string takes its steps down to depth gap_tab_k + 1 from one
+ *                                  level-table entry, one round trip for all (0: one Occ step per
+ *                                  symbol) -- same hits
  *   "kmer_k" (-1 auto, 0 off, 1..16) K-mer interval table length
  *   "gap_tab_k" (-1 auto, 0 off, 1..14) level tables of the first pass: the SA interval of every
  *                                  string of length <= K + 1 per strand; nodes at depth <= K are

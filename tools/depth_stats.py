@@ -6,7 +6,10 @@ node's reference string), for the reads the first pass resolves and for the heav
 cooperative pass takes.  Also: what fraction of the GPU's round trips (one per pop, one per tail step)
 is at a depth < K -- nodes whose SA interval is a pure function of their string, so a table of all
 strings of length <= K answers them.
-usage: tools/depth_stats.py [--reads 200000] [--normal 20000] [--heavy 2000] [--out FILE]"""
+Also: the round trips per read that a table jump of exact tails to depth K + 1 removes (k_gapped's
+gap_tail_tab), for the K a level table can have.
+usage: tools/depth_stats.py [--reads 200000] [--normal 20000] [--heavy 2000] [--out FILE]
+       tools/depth_stats.py --from-json FILE   (no GPU: the tail-jump figures of a stored histogram)"""
 import argparse
 import json
 import os
@@ -19,14 +22,38 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 
+def tail_jump_removed(tail_steps, n_reads, ks=(6, 8, 11, 12, 13, 14)):
+    """Per read, for a jump to depth K + 1: tail_steps[d] counts the steps taken from depth d, so the
+    steps from depths <= K go; a tail alive at depth d started at some depth <= d, and none ends before
+    strings stop existing (far below these K), so the tails that jump -- one round trip each, the pop's
+    own, which already carried a tail's first step -- number tail_steps[K].  Removed round trips = the
+    steps that go less those first steps."""
+    t = np.asarray(tail_steps, dtype=np.float64)
+    out = {}
+    for K in ks:
+        steps = float(t[:K + 1].sum())
+        jumps = float(t[:K + 1].max())
+        out[K] = {"tail_steps_below": round(steps / n_reads, 1), "jumps": round(jumps / n_reads, 2),
+                  "round_trips_removed": round((steps - jumps) / n_reads, 1)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--from-json", default="", help="print the tail-jump figures of a stored --out file and exit")
     ap.add_argument("--reads", type=int, default=200_000)
     ap.add_argument("--normal", type=int, default=20_000)
     ap.add_argument("--heavy", type=int, default=2_000)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.from_json:
+        with open(a.from_json) as f:
+            d = json.load(f)
+        print(json.dumps({tag: {"round_trips_per_read": d[tag]["round_trips_per_read"],
+                                "tail_jump_to_depth_K_plus_1": tail_jump_removed(d[tag]["hist"]["tail_steps"], d[tag]["n"])}
+                          for tag in ("normal", "heavy") if tag in d}, indent=1))
+        return
     import oracle
     from ibwa_amd import engine as E
     th = bench.host_threads()
@@ -64,6 +91,7 @@ def main():
                     "frac_round_trips_unique": round((uq["unique_pops"] + uq["unique_tail_steps"]) / max(tot, 1), 4),
                     "frac_round_trips_unique_match_child": round(uq["unique_match_child_pops"] / max(tot, 1), 4),
                     "frac_round_trips_unique_tail": round(uq["unique_tail_steps"] / max(tot, 1), 4),
+                    "tail_jump_to_depth_K_plus_1": tail_jump_removed(h["tail_steps"], n),
                     "frac_round_trips_below_depth": {K: round(float(cum[K - 1]), 4) for K in (8, 10, 12, 13, 14, 15, 16, 20)},
                     "frac_expansions_below_depth": {K: round(float(exp_cum[K - 1]), 4) for K in (8, 10, 12, 13, 14, 15, 16, 20)},
                     "hist": {k: [int(x) for x in v] for k, v in h.items()}}
