@@ -12,6 +12,21 @@ constexpr uint32_t ST_ALN_OVERFLOW = 2u;    // per-read hit slots exceeded      
 constexpr uint32_t ST_BAD_SCORE = 4u;       // score outside [0, n_stacks): invalid options
 constexpr uint32_t ST_HEAVY = 8u;           // iteration budget of the first pass exceeded -> retry pass
 
+// The engine's device counters: 64-bit slots of one small buffer (engine.hip, ibwa_ctx::d_counter).
+enum CounterSlot {
+  CTR_CLAIM = 0,        // a persistent launch's claim counter (every launcher zeroes it)
+  CTR_STREAM = 1,       // hit-stream fill (GapArgs / CoopArgs::aln_next; zeroed once per batch)
+  CTR_WIDE_STREAM = 2,  // fill of a wide retry launch's own hit stream
+  CTR_HANDED_ON = 3,    // count of select_handed_on
+  CTR_RESUMED = 5,      // count of select_resumed
+  CTR_TAIL_JUMPS = 7,   // GapArgs::tail_jumps
+};
+// The cooperative launches' bump pointers share another (ibwa_ctx::c_next): a u32 and, past it, a u64.
+enum CoopNextSlot {
+  CNEXT_POOL = 0,    // CoopArgs::pool_next, u32 index
+  CNEXT_PSTORE = 1,  // CoopArgs::pstore_next, u64 index
+};
+
 // Batch-level `local_opt` of bwa_cal_sa_reg_gap (bwtaln.c:86-93) as the kernels see it.
 struct AlnOpt {
   int s_mm, s_gapo, s_gape, mode;
@@ -185,8 +200,9 @@ struct CoopArgs {
   uint64_t pstore_cap;       // pstore capacity (entries)
   const uint4 *rdump;        // first-pass search states (GapArgs::rdump), roff[read] 1 + offset, 0: none
   const uint64_t *roff;
-  // resume_fixup folded in (non-null): as a read ends, fix_status[id] = 0 where it was resolved, else
-  // fix_roff[id] = 0 -- no kernel after the launch that would wait for CUs another grid holds
+  // a launch over resumed reads marks them itself (non-null): as a read ends, fix_status[id] = 0 where it
+  // was resolved (done), else fix_roff[id] = 0 (its state is dropped: the later passes run it from the
+  // start) -- no kernel after the launch that would wait for CUs another grid holds
   uint32_t *fix_status;
   uint64_t *fix_roff;
   // >= 0: the widths and N counts are the first pass's own, of read (id - wb_base) of its chunk (right
@@ -207,10 +223,6 @@ hipError_t select_handed_on(const uint32_t *status, int64_t n, int64_t *ids, uin
 hipError_t select_resumed(const uint64_t *roff, int64_t base, int64_t n, const uint32_t *status, int64_t *ids,
                           uint32_t *sel_status, unsigned long long *d_count, void *tmp, size_t *tmp_bytes,
                           hipStream_t st);
-// after a cooperative launch over resumed reads ids[0, n): status[id] = 0 where it resolved the read,
-// else roff[id] = 0 (the read starts over in the later passes)
-hipError_t resume_fixup(const uint32_t *r_status, const int64_t *ids, int64_t n, uint32_t *status, uint64_t *roff,
-                        hipStream_t st);
 // the order in which the cooperative pass takes the handed-on reads: largest first-pass stack first
 // (status bits 16-31); idx[0, n) gets the permutation of the selection, ids_out the ids in that order
 hipError_t order_heavy_first(const uint32_t *sel_status, const int64_t *ids, unsigned long long n, uint32_t *keys,
