@@ -274,6 +274,40 @@ hipError_t launch_pack_cigar(const uint32_t *cig, int cap, const int32_t *n_ciga
 uint64_t sw_words_per_lane(int max_len1, int max_len2);
 uint64_t sw_tb_per_lane(int max_len1, int max_len2);
 
+// The packed reference in HBM, refinement windows / fix-ups and MD/NM (refine.hip).
+// The resident sequence: the set's references back to back, base g at bits 7-6 .. 1-0 of byte g / 4,
+// in 32-bit words.  launch_pac_concat builds it from the references' own .pac bytes (src, reference
+// d's bytes at byte_off[d], its first base at base_off[d] of the set; base_off[n_db] = total).
+hipError_t launch_pac_concat(const uint8_t *src, const uint64_t *byte_off, const uint64_t *base_off, int n_db, uint32_t *out,
+                             uint64_t out_words, hipStream_t st);
+// dbset_extract_sequence (dbset.c:306-325) per job: codes [beg, beg + len) before l_pac to out + out_off
+hipError_t launch_pac_gather(const uint32_t *pac, uint64_t l_pac, int64_t n, const uint64_t *beg, const uint32_t *len,
+                             const uint64_t *out_off, uint8_t *out, uint32_t *got, hipStream_t st);
+// refine_gapped_core's window (bwase.c:185-192) of each job into seq1 + off1, its clipped length into len1
+hipError_t launch_refine_gather(const uint32_t *pac, uint64_t l_pac, int64_t n, const uint64_t *pos, const int32_t *ext,
+                                const uint32_t *len, const uint64_t *off1, uint8_t *seq1, uint32_t *len1, hipStream_t st);
+// k_sw's CIGAR rows (cap words each) to bwa_cigar_t with the fix-ups of bwase.c:201-218, in place
+hipError_t launch_refine_fixup(int64_t n, const uint64_t *pos, const int32_t *ext, uint32_t *cig, int cap, int32_t *n_cigar,
+                               uint64_t *pos_out, hipStream_t st);
+struct MdArgs {
+  const uint32_t *pac;
+  uint64_t l_pac;
+  int64_t n;
+  const uint64_t *pos;
+  const uint8_t *seq;        // read codes in the hit's orientation
+  const uint64_t *off;
+  const uint32_t *len;
+  const int32_t *n_cigar;    // per read; < 0: no CIGAR (nullptr: none has one)
+  const uint64_t *cig_off;   // first bwa_cigar_t of each read
+  const uint32_t *cigar;
+  uint64_t *text_off;        // n + 1: the sizing pass's text sizes (NUL included), then their exclusive scan
+  int32_t *nm;               // writing pass
+  char *text;                // writing pass
+};
+hipError_t launch_md(const MdArgs &a, bool write, hipStream_t st);
+// text_off[0, n] sizes -> offsets (text_off[n] = total); tmp == nullptr only sizes the rocPRIM scratch
+hipError_t md_scan_sizes(uint64_t *text_off, int64_t n, void *tmp, size_t *tmp_bytes, hipStream_t st);
+
 // SA row -> coordinate (sa2pos.hip): bwt_sa (bwt.c:69-79) inside bwtdb_sa2seq (dbset.c:240-246).
 struct SaArgs {
   IndexView ix[2];           // ix[0] = .bwt (strand-1 hits), ix[1] = .rbwt (strand-0 hits)

@@ -393,6 +393,11 @@ struct ibwa_ctx {
   bool kmer_valid = false;
   ibwa_run_stats_t stats = {};
   DBuf sw[15];  // sw_batch's buffers (kept between calls)
+  // the packed reference (ibwa_ctx_load_pac; lent with the index by ibwa_ctx_share_index)
+  DBuf pac;
+  uint64_t pac_len = 0;  // the set's l_pac
+  bool pac_loaded = false;
+  DBuf rf[3], md[11];  // ibwa_refine_batch's and ibwa_md_batch's buffers (kept between calls)
   // ibwa_ctx_share_index: the context whose index structures this one borrows, and how many
   // contexts borrow this one's; neither side may rebuild or replace them while shared
   ibwa_ctx *share_src = nullptr;
@@ -715,6 +720,9 @@ void ibwa_ctx_destroy(ibwa_ctx_t *c) {
     b->release();
   if (c->fqs) c->fqs->unref();
   for (auto &b : c->sw) b.release();
+  for (auto &b : c->rf) b.release();
+  for (auto &b : c->md) b.release();
+  c->pac.release();
   for (auto &x : c->ev) (void)hipEventDestroy(x);
   (void)hipStreamDestroy(c->stream);
   delete c;
@@ -893,6 +901,10 @@ int ibwa_ctx_share_index(ibwa_ctx_t *dst, const ibwa_ctx_t *src) {
     dst->sa_loaded[s] = src->sa_loaded[s];
     dst->build_rounds[s] = src->build_rounds[s];
   }
+  dst->pac.release();
+  dst->pac = src->pac.borrow();
+  dst->pac_len = src->pac_len;
+  dst->pac_loaded = src->pac_loaded;
   dst->kmer_k = src->kmer_k;
   dst->kmer_K = src->kmer_K;
   dst->gap_tab_k = src->gap_tab_k;
@@ -2643,6 +2655,94 @@ int ibwa_aln_batch(ibwa_ctx_t *c, const ibwa_gap_opt_t *opt, int64_t n, const ui
 }  // extern "C"
 
 namespace {
+// A k_sw launch in three steps, so that its inputs may come from the host (sw_batch) or be written on
+// the device (ibwa_refine_batch): sw_plan sizes the context's SW buffers (sw[0..5]: seq1, seq2, off1,
+// off2, len1, len2 -- the caller fills them on the stream), sw_launch runs the kernel, and
+// sw_fetch_cigars packs and returns the CIGAR rows once the host knows their lengths.
+struct SwPlan {
+  int max1 = 0, max2 = 0, cap = 1, blocks = 1;
+  uint64_t wpl = 0, tpl = 0;
+};
+
+int sw_plan(ibwa_ctx_t *c, int64_t n, int max1, int max2, uint64_t end1, uint64_t end2, SwPlan &P) {
+  P.max1 = max1;
+  P.max2 = max2;
+  P.cap = std::max(1, max1 + max2);
+  // the context's SW buffers, grown as needed and kept (a per-call hipMalloc / hipFree of the DP
+  // scratch cost more than the kernel on a sampe batch)
+  DBuf &s1 = c->sw[0], &s2 = c->sw[1], &o1 = c->sw[2], &o2 = c->sw[3], &l1 = c->sw[4], &l2 = c->sw[5], &sc = c->sw[6],
+       &pl = c->sw[7], &nc = c->sw[8], &en = c->sw[9], &cg = c->sw[10], &scr = c->sw[11], &tbb = c->sw[12],
+       &cf = c->sw[13];
+  P.wpl = sw_words_per_lane(max1, max2);
+  P.tpl = sw_tb_per_lane(max1, max2);
+  const uint64_t per_wave = (P.wpl * 4 + P.tpl) * 64;
+  // a persistent grid within ~32 GiB of DP scratch (5 waves per SIMD at most: 94 VGPRs)
+  const int64_t waves = std::max<int64_t>(
+      1, std::min<int64_t>({(n + 63) / 64, (int64_t)((32ull << 30) / per_wave), (int64_t)c->n_cus * 20}));
+  P.blocks = (int)((waves + 3) / 4);
+  int rc = 0;
+  if ((rc = s1.ensure(end1 + 16)) || (rc = s2.ensure(end2 + 16)) || (rc = o1.ensure(n * 8)) || (rc = o2.ensure(n * 8)) ||
+      (rc = l1.ensure(n * 4)) || (rc = l2.ensure(n * 4)) || (rc = sc.ensure(n * 4)) || (rc = pl.ensure(n * 4)) ||
+      (rc = nc.ensure(n * 4)) || (rc = en.ensure(n * 16)) || (rc = cg.ensure((uint64_t)n * P.cap * 4)) ||
+      (rc = scr.ensure((uint64_t)P.blocks * 4 * P.wpl * 4 * 64)) || (rc = tbb.ensure((uint64_t)P.blocks * 4 * P.tpl * 64)) ||
+      (rc = c->d_counter.ensure(64)) || (rc = cf.ensure(n * 8)))
+    return rc;
+  return 0;
+}
+
+// the kernel between the events ev[0] / ev[1], on the context's stream; no synchronisation
+int sw_launch(ibwa_ctx_t *c, int64_t n, const SwPlan &P, int global_band, int gap_end) {
+  SwArgs A = {};
+  A.seq1 = c->sw[0].as<uint8_t>(); A.seq2 = c->sw[1].as<uint8_t>();
+  A.off1 = c->sw[2].as<uint64_t>(); A.off2 = c->sw[3].as<uint64_t>();
+  A.len1 = c->sw[4].as<uint32_t>(); A.len2 = c->sw[5].as<uint32_t>();
+  A.n = n;
+  A.max_len1 = P.max1;
+  A.max_len2 = P.max2;
+  A.scratch = c->sw[11].as<uint32_t>(); A.words_per_lane = P.wpl;
+  A.tb = c->sw[12].as<uint8_t>(); A.tb_per_lane = P.tpl;
+  A.score = c->sw[6].as<int32_t>(); A.path_len = c->sw[7].as<int32_t>(); A.n_cigar = c->sw[8].as<int32_t>();
+  A.ends = c->sw[9].as<int4>();
+  A.cigar = c->sw[10].as<uint32_t>(); A.cigar_cap = P.cap;
+  A.stop_after = c->sw_stop_after;
+  A.global_band = global_band;
+  A.gap_end = gap_end;
+  HIPCHK(hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(launch_sw(A, counter(c, CTR_CLAIM), P.blocks, c->stream));
+  HIPCHK(hipEventRecord(c->ev[1], c->stream));
+  return 0;
+}
+
+// the CIGARs packed on the device (row p's n_cigar[p] words at its prefix offset), one copy back
+int sw_fetch_cigars(ibwa_ctx_t *c, int64_t n, const SwPlan &P, const int32_t *n_cigar, uint32_t **cigar,
+                    int64_t *n_cigar_total) {
+  DBuf &nc = c->sw[8], &cg = c->sw[10], &cf = c->sw[13], &cc = c->sw[14];
+  int rc = 0;
+  auto chk = [&](hipError_t e, const char *what) {
+    if (e != hipSuccess && !rc) rc = fail(IBWA_EHIP, "%s: %s", what, hipGetErrorString(e));
+  };
+  std::vector<uint64_t> first(n);
+  int64_t tot = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    first[p] = (uint64_t)tot;
+    tot += n_cigar[p];
+  }
+  uint32_t *o = (uint32_t *)malloc(std::max<int64_t>(tot, 1) * 4);
+  if (!o) return fail(IBWA_EINVAL, "out of host memory");
+  if (tot) {
+    if ((rc = cc.ensure((uint64_t)tot * 4))) { free(o); return rc; }
+    chk(hipMemcpyAsync(cf.p, first.data(), n * 8, hipMemcpyHostToDevice, c->stream), "H2D cigar offsets");
+    chk(launch_pack_cigar(cg.as<uint32_t>(), P.cap, nc.as<int32_t>(), cf.as<uint64_t>(), n, cc.as<uint32_t>(), c->stream),
+        "k_pack_cigar");
+    chk(hipMemcpyAsync(o, cc.p, (uint64_t)tot * 4, hipMemcpyDeviceToHost, c->stream), "D2H cigar");
+    chk(hipStreamSynchronize(c->stream), "sync");
+    if (rc) { free(o); return rc; }
+  }
+  *cigar = o;
+  if (n_cigar_total) *n_cigar_total = tot;
+  return 0;
+}
+
 // k_sw launch over host arrays: the local core (global_band == 0) or aln_global_core alone
 int sw_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64_t *off1, const uint32_t *len1,
              const uint8_t *qry, const uint64_t *off2, const uint32_t *len2, int global_band, int gap_end,
@@ -2668,28 +2768,11 @@ int sw_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64_t *off1,
     end1 = std::max<uint64_t>(end1, off1[p] + len1[p]);
     end2 = std::max<uint64_t>(end2, off2[p] + len2[p]);
   }
-  const int cap = std::max(1, max1 + max2);
-  // the context's SW buffers, grown as needed and kept (a per-call hipMalloc / hipFree of the DP
-  // scratch cost more than the kernel on a sampe batch)
+  SwPlan P;
+  if (int rc = sw_plan(c, n, max1, max2, end1, end2, P)) return rc;
   DBuf &s1 = c->sw[0], &s2 = c->sw[1], &o1 = c->sw[2], &o2 = c->sw[3], &l1 = c->sw[4], &l2 = c->sw[5], &sc = c->sw[6],
-       &pl = c->sw[7], &nc = c->sw[8], &en = c->sw[9], &cg = c->sw[10], &scr = c->sw[11], &tbb = c->sw[12],
-       &cf = c->sw[13], &cc = c->sw[14];
-  auto release = [&]() {};
-  const uint64_t wpl = sw_words_per_lane(max1, max2), tpl = sw_tb_per_lane(max1, max2);
-  const uint64_t per_wave = (wpl * 4 + tpl) * 64;
-  // a persistent grid within ~32 GiB of DP scratch (5 waves per SIMD at most: 94 VGPRs)
-  const int64_t waves = std::max<int64_t>(
-      1, std::min<int64_t>({(n + 63) / 64, (int64_t)((32ull << 30) / per_wave), (int64_t)c->n_cus * 20}));
-  const int blocks = (int)((waves + 3) / 4);
+       &pl = c->sw[7], &nc = c->sw[8], &en = c->sw[9];
   int rc = 0;
-  if ((rc = s1.ensure(end1 + 16)) || (rc = s2.ensure(end2 + 16)) || (rc = o1.ensure(n * 8)) || (rc = o2.ensure(n * 8)) ||
-      (rc = l1.ensure(n * 4)) || (rc = l2.ensure(n * 4)) || (rc = sc.ensure(n * 4)) || (rc = pl.ensure(n * 4)) ||
-      (rc = nc.ensure(n * 4)) || (rc = en.ensure(n * 16)) || (rc = cg.ensure((uint64_t)n * cap * 4)) ||
-      (rc = scr.ensure((uint64_t)blocks * 4 * wpl * 4 * 64)) || (rc = tbb.ensure((uint64_t)blocks * 4 * tpl * 64)) ||
-      (rc = c->d_counter.ensure(64)) || (rc = cf.ensure(n * 8))) {
-    release();
-    return rc;
-  }
   auto chk = [&](hipError_t e, const char *what) {
     if (e != hipSuccess && !rc) rc = fail(IBWA_EHIP, "%s: %s", what, hipGetErrorString(e));
   };
@@ -2699,26 +2782,7 @@ int sw_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64_t *off1,
   chk(hipMemcpyAsync(o2.p, off2, n * 8, hipMemcpyHostToDevice, c->stream), "H2D off2");
   chk(hipMemcpyAsync(l1.p, len1, n * 4, hipMemcpyHostToDevice, c->stream), "H2D len1");
   chk(hipMemcpyAsync(l2.p, len2, n * 4, hipMemcpyHostToDevice, c->stream), "H2D len2");
-  SwArgs A = {};
-  A.seq1 = s1.as<uint8_t>(); A.seq2 = s2.as<uint8_t>();
-  A.off1 = o1.as<uint64_t>(); A.off2 = o2.as<uint64_t>();
-  A.len1 = l1.as<uint32_t>(); A.len2 = l2.as<uint32_t>();
-  A.n = n;
-  A.max_len1 = max1;
-  A.max_len2 = max2;
-  A.scratch = scr.as<uint32_t>(); A.words_per_lane = wpl;
-  A.tb = tbb.as<uint8_t>(); A.tb_per_lane = tpl;
-  A.score = sc.as<int32_t>(); A.path_len = pl.as<int32_t>(); A.n_cigar = nc.as<int32_t>();
-  A.ends = en.as<int4>();
-  A.cigar = cg.as<uint32_t>(); A.cigar_cap = cap;
-  A.stop_after = c->sw_stop_after;
-  A.global_band = global_band;
-  A.gap_end = gap_end;
-  if (!rc) {
-    chk(hipEventRecord(c->ev[0], c->stream), "event");
-    chk(launch_sw(A, counter(c, CTR_CLAIM), blocks, c->stream), "k_sw");
-    chk(hipEventRecord(c->ev[1], c->stream), "event");
-  }
+  if (!rc) rc = sw_launch(c, n, P, global_band, gap_end);
   if (!rc) {
     chk(hipMemcpyAsync(score, sc.p, n * 4, hipMemcpyDeviceToHost, c->stream), "D2H score");
     chk(hipMemcpyAsync(path_len, pl.p, n * 4, hipMemcpyDeviceToHost, c->stream), "D2H path_len");
@@ -2729,27 +2793,7 @@ int sw_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64_t *off1,
     if (!rc && hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->stats.ms_sw = ms;
   }
   if (rc) return rc;
-  // the CIGARs packed on the device (row p's n_cigar[p] words at its prefix offset), one copy back
-  std::vector<uint64_t> first(n);
-  int64_t tot = 0;
-  for (int64_t p = 0; p < n; ++p) {
-    first[p] = (uint64_t)tot;
-    tot += n_cigar[p];
-  }
-  uint32_t *o = (uint32_t *)malloc(std::max<int64_t>(tot, 1) * 4);
-  if (!o) return fail(IBWA_EINVAL, "out of host memory");
-  if (tot) {
-    if ((rc = cc.ensure((uint64_t)tot * 4))) { free(o); return rc; }
-    chk(hipMemcpyAsync(cf.p, first.data(), n * 8, hipMemcpyHostToDevice, c->stream), "H2D cigar offsets");
-    chk(launch_pack_cigar(cg.as<uint32_t>(), cap, nc.as<int32_t>(), cf.as<uint64_t>(), n, cc.as<uint32_t>(), c->stream),
-        "k_pack_cigar");
-    chk(hipMemcpyAsync(o, cc.p, (uint64_t)tot * 4, hipMemcpyDeviceToHost, c->stream), "D2H cigar");
-    chk(hipStreamSynchronize(c->stream), "sync");
-    if (rc) { free(o); return rc; }
-  }
-  *cigar = o;
-  if (n_cigar_total) *n_cigar_total = tot;
-  return 0;
+  return sw_fetch_cigars(c, n, P, n_cigar, cigar, n_cigar_total);
 }
 }  // namespace
 
@@ -2768,6 +2812,220 @@ int ibwa_global_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64
   std::vector<int32_t> ends(4 * std::max<int64_t>(n, 1));
   return sw_batch(c, n, ref, off1, len1, qry, off2, len2, band, gap_end, score, path_len, ends.data(), n_cigar, cigar,
                   n_cigar_total);
+}
+
+int ibwa_ctx_load_pac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const uint64_t *l_pac) {
+  if (!c || n_db <= 0 || !pac || !l_pac) return fail(IBWA_EINVAL, "load_pac: bad arguments");
+  if (int rc = refuse_shared(c, "load_pac")) return rc;
+  HIPCHK(enter(c));
+  // the references' own bytes side by side (8 B-aligned starts), then the shifting concatenation
+  std::vector<uint64_t> tab(2 * (size_t)n_db + 1);
+  uint64_t *byte_off = tab.data(), *base_off = tab.data() + n_db;
+  uint64_t bytes = 0, total = 0;
+  for (int d = 0; d < n_db; ++d) {
+    if (l_pac[d] && !pac[d]) return fail(IBWA_EINVAL, "load_pac: reference %d has no bytes", d);
+    byte_off[d] = bytes;
+    base_off[d] = total;
+    bytes += ((l_pac[d] + 3) / 4 + 7) & ~7ull;
+    total += l_pac[d];
+  }
+  base_off[n_db] = total;
+  const uint64_t words = (total + 15) / 16;
+  DBuf src, dtab;
+  int rc = 0;
+  if ((rc = c->pac.ensure((words + 1) * 4)) || (rc = src.ensure(bytes + 8)) || (rc = dtab.ensure(tab.size() * 8))) {
+    src.release();
+    dtab.release();
+    return rc;
+  }
+  auto chk = [&](hipError_t e, const char *what) {
+    if (e != hipSuccess && !rc) rc = fail(IBWA_EHIP, "load_pac %s: %s", what, hipGetErrorString(e));
+  };
+  c->pac_loaded = false;
+  for (int d = 0; d < n_db; ++d)
+    if (l_pac[d])
+      chk(hipMemcpyAsync(src.as<uint8_t>() + byte_off[d], pac[d], (l_pac[d] + 3) / 4, hipMemcpyHostToDevice, c->stream), "H2D");
+  chk(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream), "H2D offsets");
+  // one word more than the sequence needs stays zero
+  chk(launch_pac_concat(src.as<uint8_t>(), dtab.as<uint64_t>(), dtab.as<uint64_t>() + n_db, n_db, c->pac.as<uint32_t>(),
+                        words + 1, c->stream), "k_pac_concat");
+  chk(hipStreamSynchronize(c->stream), "sync");
+  src.release();
+  dtab.release();
+  if (rc) return rc;
+  c->pac_len = total;
+  c->pac_loaded = true;
+  return 0;
+}
+
+int ibwa_pac_extract(ibwa_ctx_t *c, int64_t n, const uint64_t *beg, const uint32_t *len, const uint64_t *out_off,
+                     uint8_t *out, uint32_t *got) {
+  if (!c || n < 0) return fail(IBWA_EINVAL, "pac_extract: bad arguments");
+  if (!c->pac_loaded) return fail(IBWA_ENOINDEX, "no reference sequence loaded (ibwa_ctx_load_pac)");
+  if (n == 0) return 0;
+  HIPCHK(enter(c));
+  uint64_t end = 0;
+  for (int64_t p = 0; p < n; ++p) end = std::max<uint64_t>(end, out_off[p] + len[p]);
+  DBuf &db = c->rf[0], &dl = c->rf[1], &dg = c->rf[2], &dof = c->sw[2], &dout = c->sw[0];
+  int rc = 0;
+  if ((rc = db.ensure(n * 8)) || (rc = dl.ensure(n * 4)) || (rc = dg.ensure(n * 8)) || (rc = dof.ensure(n * 8)) ||
+      (rc = dout.ensure(end + 16)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(db.p, beg, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dl.p, len, n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dof.p, out_off, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(zero_async(dout.p, end, c->stream));
+  HIPCHK(launch_pac_gather(c->pac.as<uint32_t>(), c->pac_len, n, db.as<uint64_t>(), dl.as<uint32_t>(), dof.as<uint64_t>(),
+                           dout.as<uint8_t>(), dg.as<uint32_t>(), c->stream));
+  if (end) HIPCHK(hipMemcpyAsync(out, dout.p, end, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(got, dg.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int ibwa_refine_batch(ibwa_ctx_t *c, int64_t n, const uint64_t *pos, const int32_t *ext, const uint8_t *seq,
+                      const uint64_t *off, const uint32_t *len, uint64_t *pos_out, int32_t *n_cigar, uint32_t **cigar,
+                      int64_t *n_cigar_total) {
+  if (!c || n < 0 || !cigar) return fail(IBWA_EINVAL, "refine_batch: bad arguments");
+  if (!c->pac_loaded) return fail(IBWA_ENOINDEX, "no reference sequence loaded (ibwa_ctx_load_pac)");
+  // the windows' sizes before clipping: where each window goes and how large the fill can get
+  std::vector<uint64_t> off1((size_t)std::max<int64_t>(n, 1));
+  int max1 = 0, max2 = 0;
+  uint64_t end1 = 0, end2 = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    if (pos[p] > c->pac_len)  // bwase.c:179-181
+      return fail(IBWA_EINVAL, "[refine_gapped_core] job %lld: position=%llu > l_pac=%llu", (long long)p,
+                  (unsigned long long)pos[p], (unsigned long long)c->pac_len);
+    const uint64_t w = (uint64_t)len[p] + (uint64_t)std::abs((int64_t)ext[p]);
+    if (w > 0x7fffffffull || w * len[p] > (64ull << 20))
+      return fail(IBWA_EINVAL, "job %lld: %llu x %u cells is past the traceback bound", (long long)p, (unsigned long long)w,
+                  len[p]);
+    off1[p] = end1;
+    end1 += w;
+    max1 = std::max<int>(max1, (int)w);
+    max2 = std::max<int>(max2, (int)len[p]);
+    end2 = std::max<uint64_t>(end2, off[p] + len[p]);
+  }
+  *cigar = nullptr;
+  if (n_cigar_total) *n_cigar_total = 0;
+  if (n == 0) {
+    *cigar = (uint32_t *)malloc(4);
+    return 0;
+  }
+  HIPCHK(enter(c));
+  SwPlan P;
+  if (int rc = sw_plan(c, n, max1, max2, end1, end2, P)) return rc;
+  DBuf &s1 = c->sw[0], &s2 = c->sw[1], &o1 = c->sw[2], &o2 = c->sw[3], &l1 = c->sw[4], &l2 = c->sw[5], &nc = c->sw[8],
+       &cg = c->sw[10];
+  DBuf &dpos = c->rf[0], &dext = c->rf[1], &dout = c->rf[2];
+  int rc = 0;
+  if ((rc = dpos.ensure(n * 8)) || (rc = dext.ensure(n * 4)) || (rc = dout.ensure(n * 8))) return rc;
+  auto chk = [&](hipError_t e, const char *what) {
+    if (e != hipSuccess && !rc) rc = fail(IBWA_EHIP, "%s: %s", what, hipGetErrorString(e));
+  };
+  chk(hipMemcpyAsync(dpos.p, pos, n * 8, hipMemcpyHostToDevice, c->stream), "H2D pos");
+  chk(hipMemcpyAsync(dext.p, ext, n * 4, hipMemcpyHostToDevice, c->stream), "H2D ext");
+  chk(hipMemcpyAsync(s2.p, seq, end2, hipMemcpyHostToDevice, c->stream), "H2D reads");
+  chk(hipMemcpyAsync(o1.p, off1.data(), n * 8, hipMemcpyHostToDevice, c->stream), "H2D window offsets");
+  chk(hipMemcpyAsync(o2.p, off, n * 8, hipMemcpyHostToDevice, c->stream), "H2D read offsets");
+  chk(hipMemcpyAsync(l2.p, len, n * 4, hipMemcpyHostToDevice, c->stream), "H2D read lengths");
+  chk(launch_refine_gather(c->pac.as<uint32_t>(), c->pac_len, n, dpos.as<uint64_t>(), dext.as<int32_t>(), l2.as<uint32_t>(),
+                           o1.as<uint64_t>(), s1.as<uint8_t>(), l1.as<uint32_t>(), c->stream), "k_refine_gather");
+  if (!rc) rc = sw_launch(c, n, P, 50, 5);  // aln_param_bwa: band 50, gap_end 5 (stdaln.c:227)
+  if (!rc)
+    chk(launch_refine_fixup(n, dpos.as<uint64_t>(), dext.as<int32_t>(), cg.as<uint32_t>(), P.cap, nc.as<int32_t>(),
+                            dout.as<uint64_t>(), c->stream), "k_refine_fixup");
+  // the results land in the caller's arrays only once every step succeeded
+  std::vector<uint64_t> h_pos((size_t)n);
+  std::vector<int32_t> h_nc((size_t)n);
+  chk(hipMemcpyAsync(h_pos.data(), dout.p, n * 8, hipMemcpyDeviceToHost, c->stream), "D2H pos");
+  chk(hipMemcpyAsync(h_nc.data(), nc.p, n * 4, hipMemcpyDeviceToHost, c->stream), "D2H n_cigar");
+  chk(hipStreamSynchronize(c->stream), "sync");
+  if (rc) return rc;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->stats.ms_sw = ms;
+  if ((rc = sw_fetch_cigars(c, n, P, h_nc.data(), cigar, n_cigar_total))) return rc;
+  memcpy(pos_out, h_pos.data(), (size_t)n * 8);
+  memcpy(n_cigar, h_nc.data(), (size_t)n * 4);
+  return 0;
+}
+
+int ibwa_md_batch(ibwa_ctx_t *c, int64_t n, const uint64_t *pos, const uint8_t *seq, const uint64_t *off,
+                  const uint32_t *len, const int32_t *n_cigar, const uint32_t *cigar, int32_t *nm, uint64_t **md_off,
+                  const char **md) {
+  if (!c || n < 0 || !md_off || !md) return fail(IBWA_EINVAL, "md_batch: bad arguments");
+  if (!c->pac_loaded) return fail(IBWA_ENOINDEX, "no reference sequence loaded (ibwa_ctx_load_pac)");
+  *md_off = nullptr;
+  *md = nullptr;
+  std::vector<uint64_t> cig_off((size_t)n + 1, 0);
+  uint64_t end = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    cig_off[p + 1] = cig_off[p] + (uint64_t)(n_cigar && n_cigar[p] > 0 ? n_cigar[p] : 0);
+    end = std::max<uint64_t>(end, off[p] + len[p]);
+  }
+  const uint64_t n_cig = cig_off[n];
+  if (n == 0) {
+    uint64_t *o = (uint64_t *)calloc(2, 8);
+    if (!o) return fail(IBWA_EINVAL, "out of host memory");
+    *md_off = o;
+    *md = (const char *)(o + 1);
+    return 0;
+  }
+  HIPCHK(enter(c));
+  DBuf &dpos = c->md[0], &dseq = c->md[1], &doff = c->md[2], &dlen = c->md[3], &dnc = c->md[4], &dco = c->md[5],
+       &dcg = c->md[6], &dto = c->md[7], &dnm = c->md[8], &dtx = c->md[9], &dtmp = c->md[10];
+  size_t tmp_bytes = 0;
+  HIPCHK(md_scan_sizes(nullptr, n, nullptr, &tmp_bytes, c->stream));
+  int rc = 0;
+  if ((rc = dpos.ensure(n * 8)) || (rc = dseq.ensure(end + 16)) || (rc = doff.ensure(n * 8)) || (rc = dlen.ensure(n * 4)) ||
+      (rc = dnc.ensure(n * 4)) || (rc = dco.ensure((n + 1) * 8)) || (rc = dcg.ensure((n_cig + 1) * 4)) ||
+      (rc = dto.ensure((n + 1) * 8)) || (rc = dnm.ensure(n * 4)) || (rc = dtmp.ensure(std::max<size_t>(tmp_bytes, 256))))
+    return rc;
+  HIPCHK(hipMemcpyAsync(dpos.p, pos, n * 8, hipMemcpyHostToDevice, c->stream));
+  if (end) HIPCHK(hipMemcpyAsync(dseq.p, seq, end, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(doff.p, off, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dlen.p, len, n * 4, hipMemcpyHostToDevice, c->stream));
+  if (n_cigar) {
+    HIPCHK(hipMemcpyAsync(dnc.p, n_cigar, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dco.p, cig_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_cig) HIPCHK(hipMemcpyAsync(dcg.p, cigar, n_cig * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  MdArgs A = {};
+  A.pac = c->pac.as<uint32_t>();
+  A.l_pac = c->pac_len;
+  A.n = n;
+  A.pos = dpos.as<uint64_t>();
+  A.seq = dseq.as<uint8_t>();
+  A.off = doff.as<uint64_t>();
+  A.len = dlen.as<uint32_t>();
+  A.n_cigar = n_cigar ? dnc.as<int32_t>() : nullptr;
+  A.cig_off = dco.as<uint64_t>();
+  A.cigar = dcg.as<uint32_t>();
+  A.text_off = dto.as<uint64_t>();
+  A.nm = dnm.as<int32_t>();
+  // sizing pass, exclusive scan, writing pass
+  HIPCHK(launch_md(A, false, c->stream));
+  HIPCHK(md_scan_sizes(A.text_off, n, dtmp.p, &tmp_bytes, c->stream));
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(&total, A.text_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((rc = dtx.ensure(total + 16))) return rc;
+  A.text = dtx.as<char>();
+  HIPCHK(launch_md(A, true, c->stream));
+  // one allocation: the n + 1 offsets, then the texts
+  uint64_t *o = (uint64_t *)malloc((size_t)(n + 1) * 8 + total + 1);
+  if (!o) return fail(IBWA_EINVAL, "out of host memory");
+  hipError_t e = hipMemcpyAsync(o, dto.p, (n + 1) * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(o + n + 1, dtx.p, total, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(nm, dnm.p, n * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    free(o);
+    return fail(IBWA_EHIP, "md_batch: %s", hipGetErrorString(e));
+  }
+  *md_off = o;
+  *md = (const char *)(o + n + 1);
+  return 0;
 }
 
 int ibwa_occ4(ibwa_ctx_t *c, int strand, int64_t n, const uint32_t *k, uint32_t *cnt) {

@@ -331,6 +331,7 @@ struct RefDb {
 struct Dbs {
   std::vector<RefDb> db;
   uint64_t l_pac = 0;  // sum of the references' l_pac
+  bool pac_on_device = false;  // the engine contexts hold the set's sequence: refine_gapped runs on the device
   // coord2idx (dbset.c:17-39)
   int coord2idx(int64_t pos) const {
     const int count = (int)db.size();
@@ -945,11 +946,166 @@ inline void refine_finish(const Dbs &b, const Refine &j, const uint32_t *c32, in
   }
 }
 
+// Whether bwa_refine_gapped runs on the device (refine_gapped_device): IBWA_REFINE_DEVICE=1 asks for
+// it (the host path is the default: at 1 M pairs the device stage made `samse` 0.1-0.17 s and `sampe -R`
+// 0.2-0.25 s slower per command than the host threads), IBWA_REFINE_HOST=1 overrides it,
+// and no reference of the set has a remap table (their windows come from extract_remapped and their
+// CIGARs go through translate_cigar, which stay on the host).  The CLI then loads the set's .pac
+// bytes onto its engine context(s) and sets Dbs::pac_on_device.
+inline bool refine_wants_device(const Dbs &b) {
+  auto on = [](const char *name) {
+    const char *e = getenv(name);
+    return e && *e && strcmp(e, "0");
+  };
+  if (on("IBWA_REFINE_HOST") || !on("IBWA_REFINE_DEVICE")) return false;
+  for (const RefDb &r : b.db)
+    if (r.remap) return false;
+  return true;
+}
+// the set's packed references onto ctx (ibwa_ctx_load_pac); false on an error
+inline bool load_pac_to_device(ibwa_ctx_t *ctx, const Dbs &b) {
+  std::vector<const uint8_t *> pacs;
+  std::vector<uint64_t> lens;
+  for (const RefDb &r : b.db) {
+    pacs.push_back(r.bns.pac.data());
+    lens.push_back((uint64_t)r.bns.l_pac);
+  }
+  return ibwa_ctx_load_pac(ctx, (int)pacs.size(), pacs.data(), lens.data()) == 0;
+}
+
+// bwa_refine_gapped on the device, for a set without remap tables whose sequence is resident
+// (Dbs::pac_on_device): one ibwa_refine_batch for all jobs (a read's gapped multi hits, then its own
+// hit, in read order), one ibwa_md_batch at remapped_pos, then the trimmed-read correction.
+inline int refine_gapped_device(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads) {
+  const int64_t nr = (int64_t)reads.size();
+  auto own_job = [](const Read &p) {
+    return !(p.type == TYPE_NO_MATCH || p.type == TYPE_MATESW || p.n_gapo == 0);
+  };
+  std::vector<int64_t> first(nr + 1, 0);
+  std::vector<uint64_t> firstb(nr + 1, 0);
+  for (int64_t i = 0; i < nr; ++i) {
+    const Read &p = *reads[i];
+    int64_t cnt = own_job(p) ? 1 : 0;
+    for (const Multi &q : p.multi) cnt += q.gap != 0;
+    first[i + 1] = first[i] + cnt;
+    firstb[i + 1] = firstb[i] + (uint64_t)cnt * (uint64_t)p.len;
+  }
+  const int64_t m = first[nr];
+  if (m > 0) {
+    std::vector<uint64_t> pos(m), off(m), pos1(m);
+    std::vector<int32_t> ext(m), nc(m);
+    std::vector<uint32_t> len(m);
+    std::vector<uint8_t> qbuf(firstb[nr] + 1);
+    std::atomic<int64_t> bad{INT64_MAX};  // the first job whose position is out of range
+    parallel_chunks(nr, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t i = lo; i < hi; ++i) {
+        Read &p = *reads[i];
+        int64_t k = first[i];
+        uint64_t o = firstb[i];
+        auto put = [&](uint64_t ps, int e, int strand) {
+          pos[k] = ps;
+          ext[k] = e;
+          off[k] = o;
+          len[k] = (uint32_t)p.len;
+          memcpy(qbuf.data() + o, strand ? p.rseq.data() : p.seq.data(), (size_t)p.len);
+          if (ps > b.l_pac) {
+            int64_t cur = bad.load();
+            while (k < cur && !bad.compare_exchange_weak(cur, k)) {
+            }
+          }
+          ++k;
+          o += (uint64_t)p.len;
+        };
+        for (Multi &q : p.multi)
+          if (q.gap != 0) put(q.pos, (q.strand ? 1 : -1) * q.gap, q.strand);
+        if (own_job(p)) put(p.pos, (p.strand ? 1 : -1) * (p.n_gapo + p.n_gape), p.strand);
+      }
+    });
+    if (bad.load() != INT64_MAX) {
+      fprintf(stderr, "[refine_gapped_core] position=%llu > l_pac=%llu\n", (unsigned long long)pos[bad.load()],
+              (unsigned long long)b.l_pac);
+      return 1;
+    }
+    uint32_t *cg = nullptr;
+    int64_t tc = 0;
+    if (ibwa_refine_batch(ctx, m, pos.data(), ext.data(), qbuf.data(), off.data(), len.data(), pos1.data(), nc.data(), &cg,
+                          &tc))
+      return -1;
+    std::vector<int64_t> q0(m + 1, 0);
+    for (int64_t k = 0; k < m; ++k) q0[k + 1] = q0[k] + nc[k];
+    parallel_chunks(nr, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t i = lo; i < hi; ++i) {
+        Read &p = *reads[i];
+        int64_t k = first[i];
+        for (Multi &q : p.multi) {
+          if (q.gap == 0) continue;
+          q.pos = pos1[k];
+          q.cigar.assign(cg + q0[k], cg + q0[k + 1]);
+          q.has_cigar = true;
+          ++k;
+        }
+        if (own_job(p)) {
+          p.pos = pos1[k];
+          p.cigar.assign(cg + q0[k], cg + q0[k + 1]);
+          p.has_cigar = true;
+        }
+      }
+    });
+    ibwa_free(cg);
+  }
+  // MD/NM of every mapped read at its remapped_pos (bwase.c:401)
+  std::vector<int64_t> who;
+  for (int64_t i = 0; i < nr; ++i)
+    if (reads[i]->type != TYPE_NO_MATCH) who.push_back(i);
+  const int64_t nm_n = (int64_t)who.size();
+  if (nm_n > 0) {
+    std::vector<uint64_t> pos(nm_n), off(nm_n + 1, 0), coff(nm_n + 1, 0);
+    std::vector<uint32_t> len(nm_n);
+    std::vector<int32_t> nc(nm_n), nm(nm_n);
+    for (int64_t j = 0; j < nm_n; ++j) {
+      const Read &p = *reads[who[j]];
+      off[j + 1] = off[j] + (uint64_t)p.len;
+      coff[j + 1] = coff[j] + (p.has_cigar ? p.cigar.size() : 0);
+    }
+    std::vector<uint8_t> qbuf(off[nm_n] + 1);
+    std::vector<uint32_t> cbuf(coff[nm_n] + 1);
+    parallel_chunks(nm_n, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t j = lo; j < hi; ++j) {
+        const Read &p = *reads[who[j]];
+        pos[j] = p.remapped_pos;
+        len[j] = (uint32_t)p.len;
+        nc[j] = p.has_cigar ? (int32_t)p.cigar.size() : -1;
+        memcpy(qbuf.data() + off[j], p.strand ? p.rseq.data() : p.seq.data(), (size_t)p.len);
+        if (p.has_cigar && !p.cigar.empty()) memcpy(cbuf.data() + coff[j], p.cigar.data(), p.cigar.size() * 4);
+      }
+    });
+    uint64_t *moff = nullptr;
+    const char *md = nullptr;
+    if (ibwa_md_batch(ctx, nm_n, pos.data(), qbuf.data(), off.data(), len.data(), nc.data(), cbuf.data(), nm.data(), &moff,
+                      &md))
+      return -1;
+    parallel_chunks(nm_n, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t j = lo; j < hi; ++j) {
+        Read &p = *reads[who[j]];
+        p.md.assign(md + moff[j], (size_t)(moff[j + 1] - moff[j] - 1));
+        p.nm = nm[j] & 0xfff;
+        p.has_md = true;
+      }
+    });
+    ibwa_free(moff);
+  }
+  parallel_chunks(nr, [&](int64_t lo, int64_t hi, int) {
+    for (int64_t t = lo; t < hi; ++t) correct_trimmed(*reads[t]);
+  });
+  return 0;
+}
+
 // bwa_refine_gapped (bwase.c:333-416) over a set of reads: the banded global alignment of every
 // gapped hit (refine_gapped_core, bwase.c:167-241) in one ibwa_global_batch launch, then MD/NM at
 // each read's remapped_pos as the reference has it at that point (bwase.c:401) and the
 // trimmed-read correction.  Returns 0, 1 on a bad position (message printed), -1 on a GPU error.
 inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads) {
+  if (b.pac_on_device) return refine_gapped_device(ctx, b, reads);
   // the jobs in read order, gathered in contiguous read ranges on the host threads and concatenated
   struct Part {
     std::vector<Refine> jobs;

@@ -1690,6 +1690,18 @@ int sampe_main(int argc, char *argv[]) {
   }
   int gpu_rc = 0;
   for (int x : gpu_rcs) gpu_rc = gpu_rc ? gpu_rc : x;
+  host_side.join();
+  // the set's packed sequence onto each device (the context bwa_refine_gapped runs on), before the
+  // other workers borrow it with the index
+  bool host_all = true;
+  for (int d = 0; d < count; ++d) host_all = host_all && host_ok[d] >= 1;
+  if (!gpu_rc && host_all && refine_wants_device(S.dbs)) {
+    S.W[0].ph.mark("load index (first batch read meanwhile)");
+    for (int w = 0; w < n_load && !gpu_rc; ++w)
+      if (!load_pac_to_device(S.W[w].ctx[0], S.dbs)) gpu_rc = 6;
+    S.dbs.pac_on_device = !gpu_rc;
+    S.W[0].ph.mark("pac to device");
+  }
   for (int w = n_load; w < n_workers && !gpu_rc; ++w)
     for (int d = 0; d < count && !gpu_rc; ++d) {
       ibwa_ctx_t *cx = nullptr;
@@ -1697,7 +1709,7 @@ int sampe_main(int argc, char *argv[]) {
       S.W[w].ctx.push_back(cx);
       if (ibwa_ctx_share_index(cx, S.W[w % n_dev].ctx[d])) gpu_rc = 5;
     }
-  host_side.join();
+  if (gpu_rc == 6) return die("load .pac to the device");
   if (gpu_rc == 1) return die("ibwa_ctx_create");
   if (gpu_rc == 2) return die("load .bwt / .rbwt");
   if (gpu_rc == 3) return die("load .sa / .rsa");

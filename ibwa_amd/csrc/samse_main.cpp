@@ -63,6 +63,13 @@ int run_samse(Reader &rd, FILE *fp_sa, const ibwa_gap_opt_t &opt, const std::str
     return 1;
   }
   dbs.l_pac = (uint64_t)b.l_pac;
+  // the packed reference onto the device: bwa_refine_gapped's windows and MD/NM read it there
+  ph.mark("load index");
+  if (refine_wants_device(dbs)) {
+    if (!load_pac_to_device(ctx, dbs)) return die("load .pac to the device");
+    dbs.pac_on_device = true;
+    ph.mark("pac to device");
+  }
   Drand48 rnd;
   rnd.seed((long)b.seed);  // srand48(bns->seed), bwase.c:662
   Out o{out, {}};

@@ -135,6 +135,10 @@ CAPI = {
                                 _vp, _vp, c.POINTER(_u64), c.POINTER(_u64)]),
     "ibwa_sw_core_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 c.POINTER(c.c_void_p)]),
+    "ibwa_ctx_load_pac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
+    "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
+    "ibwa_md_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p)]),
 }
 
 
@@ -492,6 +496,80 @@ class Engine:
                 out.append(None)
             q += nc[p]
         return out
+
+    def load_pac(self, pacs, l_pacs):
+        """The set's references (their .pac bytes and l_pac) back to back onto the device (ibwa_ctx_load_pac)."""
+        keep = [np.ascontiguousarray(np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p,
+                                     dtype=np.uint8) for p in pacs]
+        ptrs = (c.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        ls = (c.c_uint64 * len(keep))(*[int(x) for x in l_pacs])
+        _chk(lib().ibwa_ctx_load_pac(self.h, len(keep), ptrs, ls))
+
+    def pac_extract(self, beg, lens):
+        """dbset_extract_sequence per window -> (list of uint8 code arrays of got[i] bases, got)."""
+        beg = np.ascontiguousarray(beg, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = beg.size
+        off = np.zeros(n, np.uint64)
+        if n:
+            off[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        out = np.full(int(lens.sum()) + 1, 0xFF, np.uint8)
+        got = np.zeros(n, np.uint32)
+        _chk(lib().ibwa_pac_extract(self.h, n, beg.ctypes.data, lens.ctypes.data, off.ctypes.data, out.ctypes.data,
+                                    got.ctypes.data))
+        return [out[int(off[i]):int(off[i]) + int(got[i])].copy() for i in range(n)], got
+
+    @staticmethod
+    def _pack_reads(reads):
+        n = len(reads)
+        ln = np.array([len(x) for x in reads], np.uint32)
+        off = np.zeros(n, np.uint64)
+        if n:
+            off[1:] = np.cumsum(ln[:-1], dtype=np.uint64)
+        s = np.concatenate([np.asarray(x, np.uint8) for x in reads] + [np.zeros(1, np.uint8)])
+        return s, off, ln
+
+    def refine(self, pos, ext, reads, pos_out=None, n_cigar=None):
+        """refine_gapped_core per job (ibwa_refine_batch) -> (pos' uint64[n], list of bwa_cigar_t arrays).
+        pos_out / n_cigar: the output arrays to use (tests: a failed call leaves them untouched)."""
+        n = len(reads)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        ext = np.ascontiguousarray(ext, dtype=np.int32)
+        s, off, ln = self._pack_reads(reads)
+        po = np.zeros(n, np.uint64) if pos_out is None else pos_out
+        nc = np.zeros(n, np.int32) if n_cigar is None else n_cigar
+        ptr = c.c_void_p()
+        tot = c.c_int64()
+        _chk(lib().ibwa_refine_batch(self.h, n, pos.ctypes.data, ext.ctypes.data, s.ctypes.data, off.ctypes.data,
+                                     ln.ctypes.data, po.ctypes.data, nc.ctypes.data, c.byref(ptr), c.byref(tot)))
+        cig = np.frombuffer(c.string_at(ptr.value, 4 * max(tot.value, 0)), dtype=np.uint32).copy()
+        lib().ibwa_free(ptr)
+        assert tot.value == int(nc.sum())
+        ends = np.concatenate([[0], np.cumsum(nc)])
+        return po, [cig[ends[i]:ends[i + 1]] for i in range(n)]
+
+    def md(self, pos, reads, cigars=None, raw=False):
+        """bwa_cal_md1 per read (ibwa_md_batch); cigars: None, or per read None / a bwa_cigar_t sequence.
+        -> (list of MD strings, nm int32[n]); raw=True: (offsets uint64[n + 1], text bytes, nm)."""
+        n = len(reads)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        s, off, ln = self._pack_reads(reads)
+        nc = cg = None
+        if cigars is not None:
+            nc = np.array([-1 if x is None else len(x) for x in cigars], np.int32)
+            cg = np.concatenate([np.asarray(x, np.uint32) for x in cigars if x is not None] + [np.zeros(1, np.uint32)])
+        nm = np.zeros(n, np.int32)
+        p_off, p_md = c.c_void_p(), c.c_void_p()
+        _chk(lib().ibwa_md_batch(self.h, n, pos.ctypes.data, s.ctypes.data, off.ctypes.data, ln.ctypes.data,
+                                 nc.ctypes.data if nc is not None else None, cg.ctypes.data if cg is not None else None,
+                                 nm.ctypes.data, c.byref(p_off), c.byref(p_md)))
+        offs = np.frombuffer(c.string_at(p_off.value, 8 * (n + 1)), dtype=np.uint64).copy()
+        assert p_md.value == p_off.value + 8 * (n + 1)
+        text = c.string_at(p_md.value, int(offs[n]))
+        lib().ibwa_free(p_off)
+        if raw:
+            return offs, text, nm
+        return [text[int(offs[i]):int(offs[i + 1]) - 1].decode() for i in range(n)], nm
 
     def occ4(self, strand, ks):
         ks = np.ascontiguousarray(ks, dtype=np.uint32)

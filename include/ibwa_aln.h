@@ -399,6 +399,51 @@ int ibwa_global_batch(ibwa_ctx_t *ctx, int64_t n, const uint8_t *ref, const uint
                       const uint8_t *qry, const uint64_t *off2, const uint32_t *len2, int band, int gap_end,
                       int32_t *score, int32_t *path_len, int32_t *n_cigar, uint32_t **cigar, int64_t *n_cigar_total);
 
+/*
+ * The reference sequence in HBM, and bwa_refine_gapped (bwase.c:333-416) as two batched stages.
+ *
+ * ibwa_ctx_load_pac: dbset_load_pac (dbset.c): the n_db references of a set, each 2-bit packed
+ * from its own base 0 (base x at bits 7-6 .. 1-0 of byte x / 4, bntseq.c; (l_pac[i] + 3) / 4 bytes
+ * are read of pac[i]), laid back to back as dbset_restore lays them (db[i]->offset = sum of the
+ * earlier l_pac, dbset.c:146-151) into one device array of sum(l_pac) / 4 bytes.  Loading again
+ * replaces the sequence.  ibwa_ctx_share_index lends it with the index; a context that borrows or
+ * lends its index refuses the call (IBWA_EINVAL).  The three calls below fail with IBWA_ENOINDEX
+ * while no sequence is loaded.
+ *
+ * ibwa_pac_extract: dbset_extract_sequence (dbset.c:306-325) for n windows: the codes of
+ * [beg[i], beg[i] + len[i]) clipped at the total l_pac, 1 B per base at out + out_off[i];
+ * got[i] = bases written (0 for beg[i] >= l_pac).  out is written over [0, max(out_off[i] +
+ * len[i])): the bytes no window covers, and those past got[i], are 0 (the reference callocs them).
+ *
+ * ibwa_refine_batch: refine_gapped_core (bwase.c:167-221) with is_end_correct = 1 for n hits on
+ * references without a remap table.  Job i: the hit position pos[i], ext[i] = (strand ? 1 : -1) *
+ * gaps as at bwase.c:354 / :363, and the read's codes seq[off[i] .. +len[i]) in the orientation
+ * bwa_refine_gapped passes (seq after its seq_reverse, or rseq for a reverse-strand hit).  On the
+ * device: the window rule of bwase.c:185-192, the window's bases from the resident sequence,
+ * aln_global_core with aln_param_bwa (band 50, gap_end 5), bwa_aln_path2cigar, and the position
+ * and end fix-ups of bwase.c:201-218.  pos_out[i] = the refined position, n_cigar[i], and *cigar =
+ * malloc'd concatenation of the CIGARs as bwa_cigar_t (op << 29 | len; op 0 M, 1 I, 2 D, 3 S;
+ * ibwa_free).  A job with pos > l_pac fails the whole call with IBWA_EINVAL (the message names
+ * the job, the position and l_pac, bwase.c:179-181) before anything is written.  translate_cigar
+ * of a remapped alternate (bwase.c:223-238) is the caller's, applied to this output.
+ *
+ * ibwa_md_batch: bwa_cal_md1 (bwase.c:243-295) for n reads.  Read i: pos[i], its codes in the
+ * hit's orientation, len[i], and n_cigar[i] bwa_cigar_t's (S allowed) taken in read order from
+ * `cigar`, or n_cigar[i] < 0 for none (n_cigar == NULL: no read has one).  nm[i] is unmasked (the
+ * caller keeps bwa_seq_t.nm's & 0xfff).  The MD texts come NUL-terminated and compact in read
+ * order: read i's starts at (*md)[(*md_off)[i]], (*md_off)[n] is the total size.  Offsets and
+ * texts are one allocation: release *md_off with ibwa_free (*md points into it).
+ */
+int ibwa_ctx_load_pac(ibwa_ctx_t *ctx, int n_db, const uint8_t *const *pac, const uint64_t *l_pac);
+int ibwa_pac_extract(ibwa_ctx_t *ctx, int64_t n, const uint64_t *beg, const uint32_t *len, const uint64_t *out_off,
+                     uint8_t *out, uint32_t *got);
+int ibwa_refine_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const int32_t *ext, const uint8_t *seq,
+                      const uint64_t *off, const uint32_t *len, uint64_t *pos_out, int32_t *n_cigar, uint32_t **cigar,
+                      int64_t *n_cigar_total);
+int ibwa_md_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const uint8_t *seq, const uint64_t *off,
+                  const uint32_t *len, const int32_t *n_cigar, const uint32_t *cigar, int32_t *nm, uint64_t **md_off,
+                  const char **md);
+
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
 
