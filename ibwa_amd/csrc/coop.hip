@@ -480,7 +480,15 @@ __device__ __noinline__ ResumeOut resume_state(const uint4 *rs, Shm *S, uint4 *p
 
 }  // namespace
 
-template <bool PROF>
+// EARLY: the order of a wave-iteration (the `for (;;)` of a level).  false:
+//   (a) hit barrier -> (b) commit -> (c) level end? -> (d) claims -> issue the loads -> wait -> consume
+// true: the claims and the loads go first, so (a) and (b) run while the loads are in flight:
+//   (d) claims -> issue the loads -> (a) -> (b) -> (c) -> wait -> consume
+// The loads of a chain depend only on the lane's k, l, i, ew and lst as the previous consume left
+// them, and (a) / (b) never change those: they can only discard the chain (lst = L_IDLE), which
+// the consume tests again.  What the claims then see one control section late -- barrier, cp,
+// S.head -- only makes them more conservative; see the notes at the claims and at the commit rule.
+template <bool PROF, bool EARLY>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_coop(CoopArgs A,
                                                                                      unsigned long long *counter) {
   __shared__ Shm S;
@@ -778,9 +786,140 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
             done = true;
             break;
           }
+          // what this iteration's loads were issued for, and their registers (EARLY: live across the
+          // control section)
+          bool exp = false, tail = false, qkneg = false, qshare = false;
+          uint32_t qk = 0, ql = 0, tsym = 0;
+          Blk bk, bl;
+          // (d) and the loads, one call site per order
+          auto claim_and_issue = [&]() __attribute__((always_inline)) {
+            // (d) claims: idle lanes take the next chains in pop order.
+            // EARLY: barrier, cp and S.head are what the previous iteration's control section left.
+            // cap_c and the staging-room test are then only more conservative (cp and S.head only
+            // grow), and a barrier still pending blocks the claims as before.  A hit of the previous
+            // consume is not a barrier yet, so it blocks them here (hitp): every chain claimed past it
+            // would be discarded by (a) below, and (a) keeps one hit per lane.  A chain claimed here
+            // that (a) discards all the same (a hit at a claim of this very batch) is as any other:
+            // its cstart == stg_w, so the rollback changes nothing; if it ended at its claim, its
+            // record is cleared with those of newb + 1 .. next_c.
+            {
+              const bool hitp = EARLY && __ballot(hit_c != NONE) != 0ull;
+              const bool held = barrier != NONE || hitp;
+              const uint32_t ch_max = 9u * (uint32_t)(len + 1) + 16u;
+              const bool want = lst == L_IDLE && !held && STG - (stg_w - S.head[lane]) >= ch_max;
+              const unsigned long long wm = __ballot(want);
+              const uint32_t cap_c = cp + RREC < N ? cp + RREC : N;
+              const uint32_t avail = cap_c > next_c ? cap_c - next_c : 0u;
+              const uint32_t rank = (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
+              if (prof) {
+                const bool idle = lst == L_IDLE;
+                const unsigned long long i_b = __ballot(idle && held),
+                                         i_n = __ballot(idle && !held && next_c >= N),
+                                         i_r = __ballot(idle && !held && next_c < N && next_c >= cap_c),
+                                         i_s = __ballot(idle && !held && !want);
+                if (lane == 0) {
+                  pc[12] += __popcll(i_b);
+                  pc[13] += __popcll(i_n);
+                  pc[14] += __popcll(i_r);
+                  pc[15] += __popcll(i_s);
+                }
+              }
+              if (wm) {
+                // every lane takes part in the shuffles; the claim reads its chain's window slot
+                const uint32_t cc = next_c + rank, src = cc & 63u;
+                const uint32_t tag = __shfl(wld ? wh : NONE, (int)src);
+                const uint4 ce = make_uint4(__shfl(wen.x, (int)src), __shfl(wen.y, (int)src), __shfl(wen.z, (int)src),
+                                            __shfl(wen.w, (int)src));
+                if (want && rank < avail) {
+                  c = cc;
+                  cstart = stg_w;
+                  csteps = 0;
+                  cnt0 = cnt1 = cnt2 = 0;
+                  if (tag == cc) {
+                    take_entry(ce);
+                    pop_node();
+                  } else {
+                    const uint32_t idx = N - 1u - c;  // LIFO: chain 0 is the top of the bucket
+                    ent_page = S.dirc[0][idx >> COOP_PG_LOG2];
+                    ent_off = idx & (COOP_PG - 1);
+                    lst = L_FETCH;
+                  }
+                }
+                const uint32_t nw = (uint32_t)__popcll(wm);
+                next_c += nw < avail ? nw : avail;
+                // window slots whose chain is now claimed move on to the chain 64 further
+                while (wh < next_c) {
+                  wh += 64;
+                  wld = false;
+                  wreq = wh < N;
+                }
+              }
+            }
+            lap(2);
+            // ========================================== loads of this iteration (one round trip)
+            // L2 (symbol counts) is the same for bwt and rbwt -- one text, reversed (checked at launch):
+            // the uniform copy keeps it out of the loop's vector registers
+            const int a = (int)((ew >> 24) & 1u);
+            const uint4 *ob = a ? A.o64[0] : A.o64[1];
+            if (wreq) {
+              const uint32_t widx = N - 1u - wh;
+              wen = A.pool[((uint64_t)S.dirc[0][widx >> COOP_PG_LOG2] << COOP_PG_LOG2) + (widx & (COOP_PG - 1))];
+              wld = true;
+              wreq = false;
+            }
+            exp = lst == L_EXP;
+            tail = lst == L_TAIL;
+            if (prof) {
+              const unsigned long long b_act = __ballot(lst != L_IDLE), b_f = __ballot(lst == L_FETCH),
+                                       b_t = __ballot(tail);
+              if (lane == 0) {
+                pc[9] += __popcll(b_act);
+                pc[10] += __popcll(b_f);
+                pc[11] += __popcll(b_t);
+                pc[25 + nbk] += __popcll(b_act);
+              }
+              const unsigned long long b_e1 = __ballot(exp && k == l), b_t1 = __ballot(tail && k == l);
+              if (lane == 0) {
+                pc[30] += __popcll(b_e1);
+                pc[31] += __popcll(b_t1);
+              }
+              if (lst != L_IDLE) ++csteps;
+            }
+            qk = k;
+            ql = l;
+            qkneg = qk == 0;
+            qshare = !qkneg && ((qk - 1) >> 6) == (ql >> 6);
+            tsym = tail ? sym_of(a, i) : 0u;
+            // One set of load registers: a lane fetches its chain's entry (bl.v0), takes an exact-tail
+            // step (the tail symbol's Occ words of both rows: bl.v0, bk.v0) or expands (both whole
+            // blocks) -- never two of these, so the round trip holds 8 uint4s, not 14
+            {
+              const bool fetch = lst == L_FETCH;
+              const bool kld = (exp || tail) && !qkneg && !qshare;
+              const uint4 *pl = fetch ? A.pool + (((uint64_t)ent_page << COOP_PG_LOG2) + ent_off)
+                                      : ob + ((size_t)(ql >> 6) * 4 + tsym);
+              const uint4 *pk = ob + ((size_t)((qk - 1) >> 6) * 4 + tsym);
+              if (fetch || exp || tail) bl.v0 = pl[0];
+              if (exp) {
+                bl.v1 = pl[1];
+                bl.v2 = pl[2];
+                bl.v3 = pl[3];
+              }
+              if (kld) bk.v0 = pk[0];
+              if (exp && kld) {
+                bk.v1 = pk[1];
+                bk.v2 = pk[2];
+                bk.v3 = pk[3];
+              }
+            }
+            if (EARLY) lap(3);  // (diagnostics) the issue counts with the loads' phase
+          };
+          // EARLY: the loads are in flight from here on.  They target registers only, so the breaks
+          // of the control section and (c) may leave them outstanding.
+          if constexpr (EARLY) claim_and_issue();
           // ============================================ uniform control
-          // (a) hits of chains that ended last iteration: the earliest becomes the barrier, and
-          //     every chain after it (running or finished) is discarded
+          // (a) hits of chains that ended last iteration (EARLY: or at a claim of this one): the
+          //     earliest becomes the barrier, and every chain after it (running or finished) is discarded
           {
             uint32_t newb = NONE;
             if (__ballot(hit_c != NONE)) newb = wave_min(hit_c);
@@ -841,7 +980,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
             ndone += run;
             if (run < 64) break;
           }
-          // (b) commit the finished prefix (in pop order): at least 32 chains, or all there is
+          // (b) commit the finished prefix (in pop order): at least 32 chains, or all there is.
+          // EARLY: `active` counts the lanes that claimed in this iteration too.  Progress: every
+          // claimed chain is running on a lane or finished, and a running chain takes a step per
+          // iteration, so with no commit the wave reaches active == 0, where all that is claimed
+          // commits (up to a barrier, whose hit then lifts it).  That commit advances cp and S.head, so
+          // a lane held by the chain ring or by its staging room claims in the next iteration: one
+          // iteration later than in the other order, never stuck.  The level's last commit is that
+          // case: no chain is left to claim, the last chain ended in the previous consume, active == 0,
+          // cp reaches N and (c) leaves -- in the same iteration as in the other order.  Claims that
+          // wait an iteration longer can add iterations to a level, so n_iter may reach max_iters
+          // sooner; the guard only hands the read on.
           const unsigned long long active = __ballot(lst != L_IDLE);
           uint32_t lim = ndone;
           if (barrier != NONE && lim > barrier + 1 - cp) lim = barrier + 1 - cp;
@@ -903,19 +1052,26 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
                 break;
               }
               __syncthreads();
-              // copy: the batch's children, flattened, 64 per round trip and two round trips'
-              // loads in flight (four spill registers); child g belongs to chain j with pre_j <= g < pre_j + tot_j
+              // copy: the batch's children, flattened, 64 per round trip and CU round trips'
+              // loads in flight; child g belongs to chain j with pre_j <= g < pre_j + tot_j
               // (binary search over the lanes' prefixes) and goes to its category's bucket at
               // (bucket size) + (chain's offset in the batch) + (its rank in the chain)
               {
+                // round trips' loads in flight.  EARLY holds the chains' load registers across the
+                // commit: with two, 3 VGPRs spill and the hit list's pointer is reloaded inside the
+                // chain loop (duplicate check of a gap-open hit: once per such hit).  With one,
+                // k_coop<false, true> has no scratch access in the loop and 1 VGPR spilled, but
+                // k_coop ran 38 ms per 50 M-read step slower (2 152 -> 2 190 ms, same-box A/B), so
+                // two stay; the other order with one: 4 VGPRs spilled, two reloads in the loop
+                constexpr int CU = 2;
                 const uint32_t my_rl = (ra.z >> 16) & 127, my_st = ra.x;
                 const uint32_t nb0 = S.nb[t0], nb1 = t1 < o.n_stacks ? S.nb[t1] : 0u,
                                nb2 = t2 < o.n_stacks ? S.nb[t2] : 0u;
-                for (uint32_t g0 = 0; g0 < dsum; g0 += 64u * 2) {
-                  uint4 e[2];
-                  uint32_t f0[2], f1[2], f2[2];
+                for (uint32_t g0 = 0; g0 < dsum; g0 += 64u * CU) {
+                  uint4 e[CU];
+                  uint32_t f0[CU], f1[CU], f2[CU];
 #pragma unroll
-                  for (int u = 0; u < 2; ++u) {
+                  for (int u = 0; u < CU; ++u) {
                     const uint32_t g = g0 + 64u * u + (uint32_t)lane;
                     int j = 0;
 #pragma unroll
@@ -933,7 +1089,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
                       e[u] = rl < 64 ? stg_base[((uint64_t)rl << A.stg_log2) + ((st0 + x) & SMASK)] : A.pstore[st0 + x];
                   }
 #pragma unroll
-                  for (int u = 0; u < 2; ++u) {
+                  for (int u = 0; u < CU; ++u) {
                     if (g0 + 64u * u + (uint32_t)lane < dsum) {
                       const uint32_t q = (e[u].w >> 27) & 3u, rk = e[u].z >> 20;
                       const uint32_t pos = (q == 0 ? f0[u] : q == 1 ? f1[u] : f2[u]) + rk;
@@ -1030,122 +1186,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
           lap(1);
           // (c) level finished
           if (cp == N && __ballot(lst != L_IDLE) == 0ull) break;
-          // (d) claims: idle lanes take the next chains in pop order
-          {
-            const uint32_t ch_max = 9u * (uint32_t)(len + 1) + 16u;
-            const bool want = lst == L_IDLE && barrier == NONE && STG - (stg_w - S.head[lane]) >= ch_max;
-            const unsigned long long wm = __ballot(want);
-            const uint32_t cap_c = cp + RREC < N ? cp + RREC : N;
-            const uint32_t avail = cap_c > next_c ? cap_c - next_c : 0u;
-            const uint32_t rank = (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
-            if (prof) {
-              const bool idle = lst == L_IDLE;
-              const unsigned long long i_b = __ballot(idle && barrier != NONE),
-                                       i_n = __ballot(idle && barrier == NONE && next_c >= N),
-                                       i_r = __ballot(idle && barrier == NONE && next_c < N && next_c >= cap_c),
-                                       i_s = __ballot(idle && barrier == NONE && !want);
-              if (lane == 0) {
-                pc[12] += __popcll(i_b);
-                pc[13] += __popcll(i_n);
-                pc[14] += __popcll(i_r);
-                pc[15] += __popcll(i_s);
-              }
-            }
-            if (wm) {
-              // every lane takes part in the shuffles; the claim reads its chain's window slot
-              const uint32_t cc = next_c + rank, src = cc & 63u;
-              const uint32_t tag = __shfl(wld ? wh : NONE, (int)src);
-              const uint4 ce = make_uint4(__shfl(wen.x, (int)src), __shfl(wen.y, (int)src), __shfl(wen.z, (int)src),
-                                          __shfl(wen.w, (int)src));
-              if (want && rank < avail) {
-                c = cc;
-                cstart = stg_w;
-                csteps = 0;
-                cnt0 = cnt1 = cnt2 = 0;
-                if (tag == cc) {
-                  take_entry(ce);
-                  pop_node();
-                } else {
-                  const uint32_t idx = N - 1u - c;  // LIFO: chain 0 is the top of the bucket
-                  ent_page = S.dirc[0][idx >> COOP_PG_LOG2];
-                  ent_off = idx & (COOP_PG - 1);
-                  lst = L_FETCH;
-                }
-              }
-              const uint32_t nw = (uint32_t)__popcll(wm);
-              next_c += nw < avail ? nw : avail;
-              // window slots whose chain is now claimed move on to the chain 64 further
-              while (wh < next_c) {
-                wh += 64;
-                wld = false;
-                wreq = wh < N;
-              }
-            }
-          }
-          lap(2);
-          // ============================================ loads of this iteration (one round trip)
-          // L2 (symbol counts) is the same for bwt and rbwt -- one text, reversed (checked at launch):
-          // the uniform copy keeps it out of the loop's vector registers
-          const IndexView &ix = ixv0;
-          const int a = (int)((ew >> 24) & 1u);
-          const uint4 *ob = a ? A.o64[0] : A.o64[1];
-          if (wreq) {
-            const uint32_t widx = N - 1u - wh;
-            wen = A.pool[((uint64_t)S.dirc[0][widx >> COOP_PG_LOG2] << COOP_PG_LOG2) + (widx & (COOP_PG - 1))];
-            wld = true;
-            wreq = false;
-          }
-          const bool exp = lst == L_EXP;
-          const bool tail = lst == L_TAIL;
-          if (prof) {
-            const unsigned long long b_act = __ballot(lst != L_IDLE), b_f = __ballot(lst == L_FETCH),
-                                     b_t = __ballot(tail);
-            if (lane == 0) {
-              pc[9] += __popcll(b_act);
-              pc[10] += __popcll(b_f);
-              pc[11] += __popcll(b_t);
-              pc[25 + nbk] += __popcll(b_act);
-            }
-            const unsigned long long b_e1 = __ballot(exp && k == l), b_t1 = __ballot(tail && k == l);
-            if (lane == 0) {
-              pc[30] += __popcll(b_e1);
-              pc[31] += __popcll(b_t1);
-            }
-            if (lst != L_IDLE) ++csteps;
-          }
-          const uint32_t qk = k, ql = l;
-          const bool qkneg = qk == 0;
-          const bool qshare = !qkneg && ((qk - 1) >> 6) == (ql >> 6);
-          const uint32_t tsym = tail ? sym_of(a, i) : 0u;
-          // One set of load registers: a lane fetches its chain's entry (bl.v0), takes an exact-tail
-          // step (the tail symbol's Occ words of both rows: bl.v0, bk.v0) or expands (both whole
-          // blocks) -- never two of these, so the round trip holds 8 uint4s, not 14
-          Blk bk, bl;
-          {
-            const bool fetch = lst == L_FETCH;
-            const bool kld = (exp || tail) && !qkneg && !qshare;
-            const uint4 *pl = fetch ? A.pool + (((uint64_t)ent_page << COOP_PG_LOG2) + ent_off)
-                                    : ob + ((size_t)(ql >> 6) * 4 + tsym);
-            const uint4 *pk = ob + ((size_t)((qk - 1) >> 6) * 4 + tsym);
-            if (fetch || exp || tail) bl.v0 = pl[0];
-            if (exp) {
-              bl.v1 = pl[1];
-              bl.v2 = pl[2];
-              bl.v3 = pl[3];
-            }
-            if (kld) bk.v0 = pk[0];
-            if (exp && kld) {
-              bk.v1 = pk[1];
-              bk.v2 = pk[2];
-              bk.v3 = pk[3];
-            }
-          }
+          if constexpr (!EARLY) claim_and_issue();
 
           // ============================================ consume
+          // EARLY: (a) may have discarded the chain since its loads went out (a break above leaves the
+          // loop, so no lane consumes once `done` is set); k, l, i and ew are as they were at the issue
+          const IndexView &ix = ixv0;
+          const int a = (int)((ew >> 24) & 1u);
           if (lst == L_FETCH) {
             take_entry(bl.v0);
             pop_node();
-          } else if (tail) {
+          } else if (tail && (!EARLY || lst == L_TAIL)) {
             // one step of bwt_match_exact_alt (bwt.c:240-247)
             const uint4 tvl = bl.v0;
             uint4 tvk = bk.v0;
@@ -1161,19 +1212,32 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) k_
             } else if (sym_of(a, i) > 3) {
               end_chain(false, 0, 0);
             }
-          } else if (exp) {
+          } else if (exp && (!EARLY || lst == L_EXP)) {
             // ---- expansion (bwtgap.c:200-258); the match child continues the chain.  The same steps as
             // expand_node (k_coop_roots), kept inline: through the function this loop's registers
             // spilled (16 -> 39 scratch accesses) and k_coop ran 10 % slower (same-box A/B)
-            if (qshare) bk = bl;
+            // The blocks' second words are not read.  Naming them here keeps each block four whole
+            // 16-byte loads: left to itself the compiler loads only the words read, merges
+            // neighbouring ones across the uint4s, and copies the pieces apart behind an s_waitcnt
+            // in the middle of the issue -- the row k-1 loads then went out only after the row l
+            // block had come back, two round trips per iteration instead of one.  (Row k-1's words
+            // are named in the branch below that reads its block: elsewhere bk was not loaded.)
+            // Nothing but the ISA shows that this holds: look at it again after a compiler change.
+            asm volatile("" ::"v"(bl.v1.y), "v"(bl.v2.y), "v"(bl.v3.y));
             const int e_mm = (int)(ew & 0xffu), e_go = (int)((ew >> 8) & 0xffu), e_ge = (int)((ew >> 16) & 0xffu);
             const int state = (int)((ew >> 25) & 3u);
             uint4 KK, LL;
             {
               const uint4 cl4 = make_uint4(occ_of(bl.v0, ql), occ_of(bl.v1, ql), occ_of(bl.v2, ql), occ_of(bl.v3, ql));
-              const uint4 ck4 = qkneg ? make_uint4(0, 0, 0, 0)
-                                      : make_uint4(occ_of(bk.v0, qk - 1), occ_of(bk.v1, qk - 1), occ_of(bk.v2, qk - 1),
-                                                   occ_of(bk.v3, qk - 1));
+              // row k-1 counted in its own block or (qshare) in row l's: two branches, so the two
+              // blocks' words are never merged into one set of registers (copies behind a wait)
+              uint4 ck4 = make_uint4(0, 0, 0, 0);
+              if (qshare)
+                ck4 = make_uint4(occ_of(bl.v0, qk - 1), occ_of(bl.v1, qk - 1), occ_of(bl.v2, qk - 1), occ_of(bl.v3, qk - 1));
+              else if (!qkneg) {
+                asm volatile("" ::"v"(bk.v1.y), "v"(bk.v2.y), "v"(bk.v3.y));
+                ck4 = make_uint4(occ_of(bk.v0, qk - 1), occ_of(bk.v1, qk - 1), occ_of(bk.v2, qk - 1), occ_of(bk.v3, qk - 1));
+              }
               KK = make_uint4(ix.L2[0] + ck4.x + 1, ix.L2[1] + ck4.y + 1, ix.L2[2] + ck4.z + 1, ix.L2[3] + ck4.w + 1);
               LL = make_uint4(ix.L2[0] + cl4.x, ix.L2[1] + cl4.y, ix.L2[2] + cl4.z, ix.L2[3] + cl4.w);
             }
@@ -1526,8 +1590,9 @@ hipError_t launch_coop(const CoopArgs &g, unsigned long long *d_counter, int blo
   if (e != hipSuccess) return e;
   e = zero_async(g.pool_next, sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
-  if (g.prof) hipLaunchKernelGGL(k_coop<true>, dim3(blocks), dim3(64), 0, st, g, d_counter);
-  else hipLaunchKernelGGL(k_coop<false>, dim3(blocks), dim3(64), 0, st, g, d_counter);
+  auto *kern = g.prof ? (g.early ? k_coop<true, true> : k_coop<true, false>)
+                      : (g.early ? k_coop<false, true> : k_coop<false, false>);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), 0, st, g, d_counter);
   return hipGetLastError();
 }
 

@@ -185,6 +185,7 @@ struct CoopArgs {
   uint4 *recb;               // per-wave hit records of the chain ring [COOP_RREC] (read only at a hit)
   uint32_t hcap;
   uint32_t max_iters;        // runaway guard (loop iterations per read)
+  int early;                 // the wave-iteration's order: claims and loads before the control section (k_coop EARLY)
   uint4 *aln;                // hit stream
   unsigned long long aln_total;
   unsigned long long *aln_next;

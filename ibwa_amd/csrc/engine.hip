@@ -329,6 +329,7 @@ struct ibwa_ctx {
   DBuf d_nN, d_pool, d_aoff, r_aoff, d_iters;
   // wave-cooperative heavy-read pass (coop.hip)
   int gap_coop = 1;
+  int coop_early = 1;                // k_coop issues a wave-iteration's claims and loads before its control section
   int gap_lw = 1;                    // first pass with its widths in LDS (gapped.hip LW) when they fit
   int gap_lw_min_waves = 8;          // ... in a workgroup size that keeps at least this many waves per CU
   int gap_resume = 1;                // early hand-offs leave their search state for the coop pass (LW)
@@ -779,6 +780,7 @@ int ibwa_ctx_set_option(ibwa_ctx_t *c, const char *key, long value) {
   else if (k == "diag") c->diag = value != 0;
   else if (k == "sa_walk") c->sa_walk = value != 0;
   else if (k == "gap_coop") c->gap_coop = value != 0;
+  else if (k == "coop_early" && (value == 0 || value == 1)) c->coop_early = (int)value;
   else if (k == "coop_waves_per_cu" && value > 0 && value <= 16) c->coop_waves_per_cu = (int)value;
   else if (k == "coop_pool_gb" && value >= 0 && value <= 256) c->coop_pool_gb = (int)value;
   else if (k == "coop_stg_room" && value >= 1 && value <= 4) c->coop_stg_room = (int)value;
@@ -1599,6 +1601,7 @@ CoopArgs coop_args(const Run &R, const int64_t *ids, int64_t lanes, const CoopSc
   K.recb = c->c_recb.as<uint4>();
   K.hcap = COOP_HCAP;
   K.max_iters = 1u << 24;  // runaway guard; a read past it goes to the sequential kernel
+  K.early = c->coop_early;
   // hits go on the first pass's stream (a read out of room there is flagged and re-run below)
   K.aln = c->d_aln.as<uint4>();
   K.aln_total = c->stream_total;

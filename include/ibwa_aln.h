@@ -272,6 +272,8 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *   "coop_stg_room" (1)            its per-lane staging ring holds this many chains' children (1..4)
  *   "coop_roots" (0/1, default 1)  level 0 of the heavy reads one root chain per lane (k_coop_roots)
  *   "gap_coop" (0/1, default 1)    the cooperative pass (0: heavy reads go to the wide kernel)
+ *   "coop_early" (0/1, default 1)  its wave-iterations issue their claims and loads before the hit
+ *                                  barrier and the commit (0: after them); same hits either way
  *   "sa_walk" (0/1, default 0)     SA -> coordinate by walking the sampled SA even when the full SA is
  *                                  resident
  *   Test and diagnostics hooks: "gap_stream_per_read" (4), "gap_stream_min" (1 << 20) the first
