@@ -317,6 +317,8 @@ int sampe_main(int argc, char *argv[]);  // sampe_main.cpp
 int index_main(int argc, char *argv[]);  // index_main.cpp
 int fa2pac_main(int argc, char *argv[]);
 int pac_rev_main(int argc, char *argv[]);
+int pac2cspac_main(int argc, char *argv[]);
+int index_cs_main(int argc, char *argv[]);
 
 int main(int argc, char *argv[]) {
   // Before the HIP runtime starts: host <-> device copies of every size go through the copy engines.
@@ -329,13 +331,17 @@ int main(int argc, char *argv[]) {
   if (argc >= 2 && strcmp(argv[1], "index") == 0) return index_main(argc - 1, argv + 1);
   if (argc >= 2 && strcmp(argv[1], "fa2pac") == 0) return fa2pac_main(argc - 1, argv + 1);
   if (argc >= 2 && strcmp(argv[1], "pac_rev") == 0) return pac_rev_main(argc - 1, argv + 1);
+  if (argc >= 2 && strcmp(argv[1], "pac2cspac") == 0) return pac2cspac_main(argc - 1, argv + 1);
+  if (argc >= 2 && strcmp(argv[1], "index_cs") == 0) return index_cs_main(argc - 1, argv + 1);
   if (argc < 2 || strcmp(argv[1], "aln") != 0) {
     fprintf(stderr, "Usage: ibwa-amd aln [options] <prefix> <in.fq>\n"
                     "       ibwa-amd aln [options] -f <out1.sai> -F <out2.sai> <prefix> <in1.fq> <in2.fq>\n"
                     "       ibwa-amd samse [-n max_occ] [-f out.sam] [-r RG] <prefix> <in.sai> <in.fq>\n"
                     "       ibwa-amd sampe [options] <prefix> <in1.sai> <in2.sai> <in1.fq> <in2.fq>\n"
                     "       ibwa-amd index [-a bwtsw|div|is] [-p prefix] <in.fasta>\n"
-                    "       ibwa-amd fa2pac <in.fasta> [<out.prefix>] | pac_rev <in.pac> <out.pac>\n");
+                    "       ibwa-amd index_cs [-a bwtsw|div|is] [-p prefix] <in.fasta>\n"
+                    "       ibwa-amd fa2pac <in.fasta> [<out.prefix>] | pac_rev <in.pac> <out.pac>\n"
+                    "       ibwa-amd pac2cspac <in.nt.prefix> <out.cs.prefix>\n");
     return 1;
   }
   --argc; ++argv;

@@ -309,6 +309,33 @@ hipError_t launch_md(const MdArgs &a, bool write, hipStream_t st);
 // text_off[0, n] sizes -> offsets (text_off[n] = total); tmp == nullptr only sizes the rocPRIM scratch
 hipError_t md_scan_sizes(uint64_t *text_off, int64_t n, void *tmp, size_t *tmp_bytes, hipStream_t st);
 
+// Colour space (cs2nt.hip).
+// bwa_pac2cspac_core (bwtmisc.c:202-219): the colour sequence of `words` words of a packed nucleotide
+// sequence (the resident layout above); nt[words - 1] covers base l_pac - 1, bits past l_pac come out 0
+hipError_t launch_pac2cs(const uint32_t *nt, uint64_t l_pac, uint32_t *cs, uint64_t words, hipStream_t st);
+// cs2nt_DP + cs2nt_nt_qual (cs2nt.c:37-110) of jobs [first, min(first + lanes, n)), one per lane
+struct Cs2ntArgs {
+  int64_t n, first, lanes;   // lanes: a multiple of 256, the launch's threads and the scratch's row length
+  const uint32_t *size;      // per job: colours in its rows (>= 1)
+  const uint64_t *off;       // per job: its rows (caller's rows) or its read (rows from the sequence)
+  uint8_t *bt, *cs;          // scratch, (max size + 1) * lanes bytes each, position-major
+  uint8_t *out;              // size - 1 bytes of base << 6 | qual per job, at out + out_off[job]
+  const uint64_t *out_off;
+  // the caller's rows: nt_ref[off .. off + size], cs_read[off .. off + size)
+  const uint8_t *nt_ref, *cs_read;
+  // rows from the resident nucleotide sequence (bwa_cs2nt_core, cs2nt.c:136-171)
+  const uint32_t *pac;
+  uint64_t l_pac;
+  const uint64_t *pos;
+  const uint8_t *strand;
+  const uint8_t *seq, *qual;  // the read's colour codes in the hit's orientation; its quality string as read
+  const uint32_t *len;
+  const int32_t *n_cigar;     // <= 0: none
+  const uint64_t *cig_off;
+  const uint32_t *cigar;      // bwa_cigar_t
+};
+hipError_t launch_cs2nt(const Cs2ntArgs &a, bool from_pac, hipStream_t st);
+
 // SA row -> coordinate (sa2pos.hip): bwt_sa (bwt.c:69-79) inside bwtdb_sa2seq (dbset.c:240-246).
 struct SaArgs {
   IndexView ix[2];           // ix[0] = .bwt (strand-1 hits), ix[1] = .rbwt (strand-0 hits)

@@ -399,6 +399,11 @@ struct ibwa_ctx {
   uint64_t pac_len = 0;  // the set's l_pac
   bool pac_loaded = false;
   DBuf rf[3], md[11];  // ibwa_refine_batch's and ibwa_md_batch's buffers (kept between calls)
+  // the nucleotide sequence of a colour-space set (ibwa_ctx_load_ntpac; lent like pac)
+  DBuf ntpac;
+  uint64_t ntpac_len = 0;
+  bool ntpac_loaded = false;
+  DBuf cs[14];  // ibwa_cs2nt_rows' / ibwa_cs2nt_batch's buffers (kept between calls)
   // ibwa_ctx_share_index: the context whose index structures this one borrows, and how many
   // contexts borrow this one's; neither side may rebuild or replace them while shared
   ibwa_ctx *share_src = nullptr;
@@ -724,6 +729,8 @@ void ibwa_ctx_destroy(ibwa_ctx_t *c) {
   for (auto &b : c->rf) b.release();
   for (auto &b : c->md) b.release();
   c->pac.release();
+  c->ntpac.release();
+  for (auto &b : c->cs) b.release();
   for (auto &x : c->ev) (void)hipEventDestroy(x);
   (void)hipStreamDestroy(c->stream);
   delete c;
@@ -907,6 +914,10 @@ int ibwa_ctx_share_index(ibwa_ctx_t *dst, const ibwa_ctx_t *src) {
   dst->pac = src->pac.borrow();
   dst->pac_len = src->pac_len;
   dst->pac_loaded = src->pac_loaded;
+  dst->ntpac.release();
+  dst->ntpac = src->ntpac.borrow();
+  dst->ntpac_len = src->ntpac_len;
+  dst->ntpac_loaded = src->ntpac_loaded;
   dst->kmer_k = src->kmer_k;
   dst->kmer_K = src->kmer_K;
   dst->gap_tab_k = src->gap_tab_k;
@@ -2817,9 +2828,9 @@ int ibwa_global_batch(ibwa_ctx_t *c, int64_t n, const uint8_t *ref, const uint64
                   n_cigar_total);
 }
 
-int ibwa_ctx_load_pac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const uint64_t *l_pac) {
-  if (!c || n_db <= 0 || !pac || !l_pac) return fail(IBWA_EINVAL, "load_pac: bad arguments");
-  if (int rc = refuse_shared(c, "load_pac")) return rc;
+// the n_db references' .pac bytes back to back into `dst` (ibwa_ctx_load_pac / ibwa_ctx_load_ntpac)
+static int load_pac_set(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const uint64_t *l_pac, DBuf &dst, uint64_t &dst_len,
+                        bool &dst_loaded) {
   HIPCHK(enter(c));
   // the references' own bytes side by side (8 B-aligned starts), then the shifting concatenation
   std::vector<uint64_t> tab(2 * (size_t)n_db + 1);
@@ -2836,7 +2847,7 @@ int ibwa_ctx_load_pac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const 
   const uint64_t words = (total + 15) / 16;
   DBuf src, dtab;
   int rc = 0;
-  if ((rc = c->pac.ensure((words + 1) * 4)) || (rc = src.ensure(bytes + 8)) || (rc = dtab.ensure(tab.size() * 8))) {
+  if ((rc = dst.ensure((words + 1) * 4)) || (rc = src.ensure(bytes + 8)) || (rc = dtab.ensure(tab.size() * 8))) {
     src.release();
     dtab.release();
     return rc;
@@ -2844,21 +2855,33 @@ int ibwa_ctx_load_pac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const 
   auto chk = [&](hipError_t e, const char *what) {
     if (e != hipSuccess && !rc) rc = fail(IBWA_EHIP, "load_pac %s: %s", what, hipGetErrorString(e));
   };
-  c->pac_loaded = false;
+  dst_loaded = false;
   for (int d = 0; d < n_db; ++d)
     if (l_pac[d])
       chk(hipMemcpyAsync(src.as<uint8_t>() + byte_off[d], pac[d], (l_pac[d] + 3) / 4, hipMemcpyHostToDevice, c->stream), "H2D");
   chk(hipMemcpyAsync(dtab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream), "H2D offsets");
   // one word more than the sequence needs stays zero
-  chk(launch_pac_concat(src.as<uint8_t>(), dtab.as<uint64_t>(), dtab.as<uint64_t>() + n_db, n_db, c->pac.as<uint32_t>(),
+  chk(launch_pac_concat(src.as<uint8_t>(), dtab.as<uint64_t>(), dtab.as<uint64_t>() + n_db, n_db, dst.as<uint32_t>(),
                         words + 1, c->stream), "k_pac_concat");
   chk(hipStreamSynchronize(c->stream), "sync");
   src.release();
   dtab.release();
   if (rc) return rc;
-  c->pac_len = total;
-  c->pac_loaded = true;
+  dst_len = total;
+  dst_loaded = true;
   return 0;
+}
+
+int ibwa_ctx_load_pac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const uint64_t *l_pac) {
+  if (!c || n_db <= 0 || !pac || !l_pac) return fail(IBWA_EINVAL, "load_pac: bad arguments");
+  if (int rc = refuse_shared(c, "load_pac")) return rc;
+  return load_pac_set(c, n_db, pac, l_pac, c->pac, c->pac_len, c->pac_loaded);
+}
+
+int ibwa_ctx_load_ntpac(ibwa_ctx_t *c, int n_db, const uint8_t *const *pac, const uint64_t *l_pac) {
+  if (!c || n_db <= 0 || !pac || !l_pac) return fail(IBWA_EINVAL, "load_ntpac: bad arguments");
+  if (int rc = refuse_shared(c, "load_ntpac")) return rc;
+  return load_pac_set(c, n_db, pac, l_pac, c->ntpac, c->ntpac_len, c->ntpac_loaded);
 }
 
 int ibwa_pac_extract(ibwa_ctx_t *c, int64_t n, const uint64_t *beg, const uint32_t *len, const uint64_t *out_off,
@@ -3028,6 +3051,162 @@ int ibwa_md_batch(ibwa_ctx_t *c, int64_t n, const uint64_t *pos, const uint8_t *
   }
   *md_off = o;
   *md = (const char *)(o + n + 1);
+  return 0;
+}
+
+int ibwa_pac2cspac(ibwa_ctx_t *c, const uint8_t *nt_pac, uint64_t l_pac, uint8_t *cs_pac_out) {
+  if (!c || !nt_pac || !cs_pac_out || l_pac == 0) return fail(IBWA_EINVAL, "pac2cspac: bad arguments");
+  HIPCHK(enter(c));
+  const uint64_t in_bytes = (l_pac + 3) / 4, out_bytes = l_pac / 4 + 1, words = (l_pac + 15) / 16;
+  DBuf &din = c->cs[0], &dout = c->cs[1];
+  int rc = 0;
+  // one word more than the sequence needs: l_pac / 4 + 1 bytes can end in the word after the last base
+  if ((rc = din.ensure((words + 1) * 4)) || (rc = dout.ensure((words + 1) * 4))) return rc;
+  HIPCHK(zero_async(din.as<uint8_t>() + (words - 1) * 4, 8, c->stream));
+  HIPCHK(hipMemcpyAsync(din.p, nt_pac, in_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(launch_pac2cs(din.as<uint32_t>(), l_pac, dout.as<uint32_t>(), words + 1, c->stream));
+  HIPCHK(hipMemcpyAsync(cs_pac_out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+namespace {
+// the launches of k_cs2nt over n jobs whose per-job arrays are on the device: the position-major
+// scratch holds `lanes` jobs at a time (at most CS_SCRATCH bytes), so a large batch takes several
+constexpr uint64_t CS_SCRATCH = 512ull << 20;
+int cs2nt_run(ibwa_ctx *c, Cs2ntArgs &A, uint32_t max_size, bool from_pac) {
+  const uint64_t per_lane = 2 * ((uint64_t)max_size + 1);
+  int64_t lanes = (A.n + 255) & ~255ll;
+  lanes = std::min<int64_t>(lanes, std::max<int64_t>(256, (int64_t)(CS_SCRATCH / per_lane) & ~255ll));
+  DBuf &dbt = c->cs[2];
+  if (int rc = dbt.ensure(per_lane * (uint64_t)lanes)) return rc;
+  A.lanes = lanes;
+  A.bt = dbt.as<uint8_t>();
+  A.cs = A.bt + ((uint64_t)max_size + 1) * (uint64_t)lanes;
+  for (A.first = 0; A.first < A.n; A.first += lanes) HIPCHK(launch_cs2nt(A, from_pac, c->stream));
+  return 0;
+}
+}  // namespace
+
+int ibwa_cs2nt_rows(ibwa_ctx_t *c, int64_t n, const uint8_t *nt_ref, const uint8_t *cs_read, const uint64_t *off,
+                    const uint32_t *size, uint8_t *out, const uint64_t *out_off) {
+  if (!c || n < 0 || (n && (!nt_ref || !cs_read || !off || !size || !out || !out_off)))
+    return fail(IBWA_EINVAL, "cs2nt_rows: bad arguments");
+  uint64_t end = 0, out_end = 0;
+  uint32_t max_size = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    if (size[p] == 0 || size[p] > 0x7ffffffeu)  // cs2nt_nt_qual's loop (cs2nt.c:95) does not end at size 0
+      return fail(IBWA_EINVAL, "cs2nt_rows: job %lld has size %u", (long long)p, size[p]);
+    end = std::max<uint64_t>(end, off[p] + size[p] + 1);
+    out_end = std::max<uint64_t>(out_end, out_off[p] + size[p] - 1);
+    max_size = std::max(max_size, size[p]);
+  }
+  if (n == 0) return 0;
+  HIPCHK(enter(c));
+  DBuf &dref = c->cs[3], &dcs = c->cs[4], &doff = c->cs[5], &dsz = c->cs[6], &dout = c->cs[7], &doo = c->cs[8];
+  int rc = 0;
+  if ((rc = dref.ensure(end)) || (rc = dcs.ensure(end)) || (rc = doff.ensure(n * 8)) || (rc = dsz.ensure(n * 4)) ||
+      (rc = dout.ensure(out_end + 16)) || (rc = doo.ensure(n * 8)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(dref.p, nt_ref, end, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dcs.p, cs_read, end - 1, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(doff.p, off, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dsz.p, size, n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(doo.p, out_off, n * 8, hipMemcpyHostToDevice, c->stream));
+  Cs2ntArgs A = {};
+  A.n = n;
+  A.size = dsz.as<uint32_t>();
+  A.off = doff.as<uint64_t>();
+  A.out = dout.as<uint8_t>();
+  A.out_off = doo.as<uint64_t>();
+  A.nt_ref = dref.as<uint8_t>();
+  A.cs_read = dcs.as<uint8_t>();
+  if ((rc = cs2nt_run(c, A, max_size, false))) return rc;
+  // only the jobs' own size - 1 bytes are the caller's to overwrite
+  std::vector<uint8_t> h(out_end);
+  if (out_end) HIPCHK(hipMemcpyAsync(h.data(), dout.p, out_end, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t p = 0; p < n; ++p) memcpy(out + out_off[p], h.data() + out_off[p], size[p] - 1);
+  return 0;
+}
+
+int ibwa_cs2nt_batch(ibwa_ctx_t *c, int64_t n, const uint64_t *pos, const uint8_t *strand, const uint8_t *seq,
+                     const uint8_t *qual, const uint64_t *off, const uint32_t *len, const int32_t *n_cigar,
+                     const uint32_t *cigar, uint8_t *out, uint32_t *new_len) {
+  if (!c || n < 0 || (n && (!pos || !strand || !seq || !qual || !off || !len || !out || !new_len)))
+    return fail(IBWA_EINVAL, "cs2nt_batch: bad arguments");
+  if (!c->ntpac_loaded) return fail(IBWA_ENOINDEX, "no nucleotide sequence loaded (ibwa_ctx_load_ntpac)");
+  if (n == 0) return 0;
+  // the rows' sizes (cs2nt.c:143-171: every M and I colour), checked against the read
+  std::vector<uint32_t> size((size_t)n);
+  std::vector<uint64_t> cig_off((size_t)n + 1, 0);
+  std::vector<int32_t> nc((size_t)n, 0);
+  uint64_t end = 0;
+  uint32_t max_size = 0;
+  for (int64_t p = 0; p < n; ++p) {
+    nc[p] = n_cigar && n_cigar[p] > 0 ? n_cigar[p] : 0;
+    cig_off[p + 1] = cig_off[p] + (uint64_t)nc[p];
+    uint64_t rows = len[p], used = len[p];
+    if (nc[p]) {
+      if (!cigar) return fail(IBWA_EINVAL, "cs2nt_batch: read %lld has a CIGAR count and no CIGAR", (long long)p);
+      rows = used = 0;
+      for (int k = 0; k < nc[p]; ++k) {
+        const uint32_t w = cigar[cig_off[p] + k], op = w >> 29, l = w & 0x1fffffffu;
+        if (op > 3) return fail(IBWA_EINVAL, "cs2nt_batch: read %lld: CIGAR operation %u", (long long)p, op);
+        if (op == 0 || op == 1) rows += l;
+        if (op != 2) used += l;
+      }
+    }
+    if (rows == 0 || used > len[p])
+      return fail(IBWA_EINVAL, "cs2nt_batch: read %lld: %llu row colours, %llu of %u read colours used", (long long)p,
+                  (unsigned long long)rows, (unsigned long long)used, len[p]);
+    size[p] = (uint32_t)rows;
+    max_size = std::max(max_size, size[p]);
+    end = std::max<uint64_t>(end, off[p] + len[p]);
+  }
+  const uint64_t n_cig = cig_off[n];
+  HIPCHK(enter(c));
+  DBuf &dseq = c->cs[3], &dq = c->cs[4], &doff = c->cs[5], &dsz = c->cs[6], &dout = c->cs[7], &dpos = c->cs[8],
+       &dst = c->cs[9], &dlen = c->cs[10], &dnc = c->cs[11], &dco = c->cs[12], &dcg = c->cs[13];
+  int rc = 0;
+  if ((rc = dseq.ensure(end)) || (rc = dq.ensure(end)) || (rc = doff.ensure(n * 8)) || (rc = dsz.ensure(n * 4)) ||
+      (rc = dout.ensure(end + 16)) || (rc = dpos.ensure(n * 8)) || (rc = dst.ensure(n)) || (rc = dlen.ensure(n * 4)) ||
+      (rc = dnc.ensure(n * 4)) || (rc = dco.ensure((n + 1) * 8)) || (rc = dcg.ensure((n_cig + 1) * 4)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(dseq.p, seq, end, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dq.p, qual, end, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(doff.p, off, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dsz.p, size.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dpos.p, pos, n * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dst.p, strand, n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dlen.p, len, n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dnc.p, nc.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dco.p, cig_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if (n_cig) HIPCHK(hipMemcpyAsync(dcg.p, cigar, n_cig * 4, hipMemcpyHostToDevice, c->stream));
+  Cs2ntArgs A = {};
+  A.n = n;
+  A.size = dsz.as<uint32_t>();
+  A.off = doff.as<uint64_t>();
+  A.out = dout.as<uint8_t>();
+  A.out_off = doff.as<uint64_t>();  // a read's bases go where its colours were: size - 1 < len
+  A.pac = c->ntpac.as<uint32_t>();
+  A.l_pac = c->ntpac_len;
+  A.pos = dpos.as<uint64_t>();
+  A.strand = dst.as<uint8_t>();
+  A.seq = dseq.as<uint8_t>();
+  A.qual = dq.as<uint8_t>();
+  A.len = dlen.as<uint32_t>();
+  A.n_cigar = dnc.as<int32_t>();
+  A.cig_off = dco.as<uint64_t>();
+  A.cigar = dcg.as<uint32_t>();
+  if ((rc = cs2nt_run(c, A, max_size, true))) return rc;
+  std::vector<uint8_t> h(end);
+  HIPCHK(hipMemcpyAsync(h.data(), dout.p, end, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t p = 0; p < n; ++p) {
+    memcpy(out + off[p], h.data() + off[p], size[p] - 1);
+    new_len[p] = size[p] - 1;
+  }
   return 0;
 }
 

@@ -8,7 +8,12 @@
 //   index    both, then .bwt/.rbwt (bwt_pac2bwt + bwt_bwtupdate_core, i.e. the interleaved
 //            layout) and .sa/.rsa (bwt_cal_sa, interval 32) from one ibwa_ctx_build_index call
 //            (on-device prefix-doubling suffix sort, bit-identical to `bwa index -a is`).
-//            -a is / bwtsw / div all give the same files; -c (color space) is rejected.
+//            -a is / bwtsw / div all give the same files; -c (color space) is rejected:
+//            the colour index has its own subcommand until `index -c` is routed to it;
+//   pac2cspac  bwa_pac2cspac (bwtmisc.c:221-246): the colour .pac of a nucleotide .pac (k_pac2cs on the
+//            device), with the .ann / .amb copied;
+//   index_cs the file set of `bwa index -c` (bwtindex.c:85-101, then the common tail): fa2pac to
+//            <prefix>.nt, pac2cspac to <prefix>, then .rpac / .bwt / .rbwt / .sa / .rsa of the colours.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -149,6 +154,83 @@ bool write_words(const std::string &fn, const std::vector<uint32_t> &head, const
   return fclose(fp) == 0 && ok;
 }
 
+// .bwt / .rbwt / .sa / .rsa of the packed text from one ibwa_ctx_build_index call
+int build_bwt_sa(ibwa_ctx_t *ctx, const std::string &prefix, const Packed &pk) {
+  ibwa_ctx_set_option(ctx, "exact_jump", 0);  // the CLI only exports the files
+  if (ibwa_ctx_build_index(ctx, pk.codes.data(), (uint64_t)pk.l_pac, 32)) return die("build index");
+  const char *ext_bwt[2] = {".bwt", ".rbwt"}, *ext_sa[2] = {".sa", ".rsa"};
+  for (int s = 0; s < 2; ++s) {
+    uint32_t primary = 0, L2[4];
+    uint64_t bwt_size = 0;
+    if (ibwa_ctx_bwt_info(ctx, s, &primary, L2, &bwt_size)) return die("bwt info");
+    std::vector<uint32_t> w(bwt_size);
+    if (ibwa_ctx_export_bwt(ctx, s, w.data(), bwt_size)) return die("export bwt");
+    // bwt_dump_bwt (bwtio.c:7-15): primary, L2[1..4], the interleaved words
+    if (!write_words(prefix + ext_bwt[s], {primary, L2[0], L2[1], L2[2], L2[3]}, w.data(), w.size())) {
+      fprintf(stderr, "[ibwa-amd index] cannot write %s%s\n", prefix.c_str(), ext_bwt[s]);
+      return 1;
+    }
+    const uint64_t seq_len = (uint64_t)pk.l_pac, n_sa = (seq_len + 32) / 32;
+    std::vector<uint32_t> sa(n_sa);
+    if (ibwa_ctx_export_sa(ctx, s, sa.data(), n_sa)) return die("export sa");
+    // bwt_dump_sa (bwtio.c:17-27): primary, L2[1..4], sa_intv, seq_len, sa[1..n_sa)
+    if (!write_words(prefix + ext_sa[s], {primary, L2[0], L2[1], L2[2], L2[3], 32u, (uint32_t)seq_len}, sa.data() + 1,
+                     n_sa - 1)) {
+      fprintf(stderr, "[ibwa-amd index] cannot write %s%s\n", prefix.c_str(), ext_sa[s]);
+      return 1;
+    }
+  }
+  return 0;
+}
+
+bool read_file(const std::string &fn, std::vector<uint8_t> &out) {
+  FILE *fp = fopen(fn.c_str(), "rb");
+  if (!fp) return false;
+  out.clear();
+  uint8_t buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, fp)) > 0) out.insert(out.end(), buf, buf + got);
+  fclose(fp);
+  return true;
+}
+
+bool write_file(const std::string &fn, const std::vector<uint8_t> &data) {
+  FILE *fp = fopen(fn.c_str(), "wb");
+  if (!fp) return false;
+  const bool ok = fwrite(data.data(), 1, data.size(), fp) == data.size();
+  return fclose(fp) == 0 && ok;
+}
+
+// bwa_pac2cspac (bwtmisc.c:221-246): <in>.ann / .amb as they are (bns_restore + bns_dump), and the colour
+// .pac from the device: l_pac / 4 + 1 bytes, then l_pac % 4.  cs (optional) gets one colour per byte.
+int pac2cspac(ibwa_ctx_t *ctx, const std::string &in, const std::string &out, Packed *cs) {
+  std::vector<uint8_t> ann, amb, pac;
+  for (auto f : {std::make_pair(".ann", &ann), std::make_pair(".amb", &amb), std::make_pair(".pac", &pac)})
+    if (!read_file(in + f.first, *f.second)) {
+      fprintf(stderr, "[ibwa-amd pac2cspac] cannot open %s%s\n", in.c_str(), f.first);
+      return 1;
+    }
+  long long l_pac = 0;  // bns_restore (bntseq.c:95): the first number of the .ann
+  if (sscanf(std::string(ann.begin(), ann.end()).c_str(), "%lld", &l_pac) != 1 || l_pac <= 0 ||
+      pac.size() < (size_t)(l_pac + 3) / 4) {
+    fprintf(stderr, "[ibwa-amd pac2cspac] %s.ann / .pac: no sequence of the length the .ann gives\n", in.c_str());
+    return 1;
+  }
+  std::vector<uint8_t> cspac((size_t)l_pac / 4 + 1);
+  if (ibwa_pac2cspac(ctx, pac.data(), (uint64_t)l_pac, cspac.data())) return die("pac2cspac");
+  if (cs) {
+    cs->l_pac = l_pac;
+    cs->codes.resize((size_t)l_pac);
+    for (long long i = 0; i < l_pac; ++i) cs->codes[i] = cspac[i >> 2] >> ((~i & 3) << 1) & 3;
+  }
+  cspac.push_back((uint8_t)(l_pac % 4));
+  if (!write_file(out + ".ann", ann) || !write_file(out + ".amb", amb) || !write_file(out + ".pac", cspac)) {
+    fprintf(stderr, "[ibwa-amd pac2cspac] cannot write %s.{ann,amb,pac}\n", out.c_str());
+    return 1;
+  }
+  return 0;
+}
+
 }  // namespace
 
 int fa2pac_main(int argc, char *argv[]) {
@@ -200,30 +282,54 @@ int index_main(int argc, char *argv[]) {
   }
   ibwa_ctx_t *ctx = nullptr;
   if (ibwa_ctx_create(0, &ctx)) return die("ibwa_ctx_create");
-  ibwa_ctx_set_option(ctx, "exact_jump", 0);  // the CLI only exports the files
-  if (ibwa_ctx_build_index(ctx, pk.codes.data(), (uint64_t)pk.l_pac, 32)) return die("build index");
-  const char *ext_bwt[2] = {".bwt", ".rbwt"}, *ext_sa[2] = {".sa", ".rsa"};
-  for (int s = 0; s < 2; ++s) {
-    uint32_t primary = 0, L2[4];
-    uint64_t bwt_size = 0;
-    if (ibwa_ctx_bwt_info(ctx, s, &primary, L2, &bwt_size)) return die("bwt info");
-    std::vector<uint32_t> w(bwt_size);
-    if (ibwa_ctx_export_bwt(ctx, s, w.data(), bwt_size)) return die("export bwt");
-    // bwt_dump_bwt (bwtio.c:7-15): primary, L2[1..4], the interleaved words
-    if (!write_words(prefix + ext_bwt[s], {primary, L2[0], L2[1], L2[2], L2[3]}, w.data(), w.size())) {
-      fprintf(stderr, "[ibwa-amd index] cannot write %s%s\n", prefix.c_str(), ext_bwt[s]);
-      return 1;
-    }
-    const uint64_t seq_len = (uint64_t)pk.l_pac, n_sa = (seq_len + 32) / 32;
-    std::vector<uint32_t> sa(n_sa);
-    if (ibwa_ctx_export_sa(ctx, s, sa.data(), n_sa)) return die("export sa");
-    // bwt_dump_sa (bwtio.c:17-27): primary, L2[1..4], sa_intv, seq_len, sa[1..n_sa)
-    if (!write_words(prefix + ext_sa[s], {primary, L2[0], L2[1], L2[2], L2[3], 32u, (uint32_t)seq_len}, sa.data() + 1,
-                     n_sa - 1)) {
-      fprintf(stderr, "[ibwa-amd index] cannot write %s%s\n", prefix.c_str(), ext_sa[s]);
-      return 1;
+  const int rc = build_bwt_sa(ctx, prefix, pk);
+  ibwa_ctx_destroy(ctx);
+  return rc;
+}
+
+int pac2cspac_main(int argc, char *argv[]) {
+  if (argc < 3) {
+    fprintf(stderr, "Usage: ibwa-amd pac2cspac <in.nt.prefix> <out.cs.prefix>\n");
+    return 1;
+  }
+  ibwa_ctx_t *ctx = nullptr;
+  if (ibwa_ctx_create(0, &ctx)) return die("ibwa_ctx_create");
+  const int rc = pac2cspac(ctx, argv[1], argv[2], nullptr);
+  ibwa_ctx_destroy(ctx);
+  return rc;
+}
+
+int index_cs_main(int argc, char *argv[]) {
+  std::string prefix;
+  int c;
+  optind = 1;
+  while ((c = getopt(argc, argv, "a:p:")) >= 0) {  // bwa_index (bwtindex.c:48-60) with -c given
+    switch (c) {
+      case 'a':
+        if (strcmp(optarg, "div") && strcmp(optarg, "bwtsw") && strcmp(optarg, "is")) {
+          fprintf(stderr, "[bwa_index] unknown algorithm: '%s'.\n", optarg);
+          return 1;
+        }
+        break;
+      case 'p': prefix = optarg; break;
+      default: return 1;
     }
   }
+  if (optind + 1 > argc) {
+    fprintf(stderr, "Usage: ibwa-amd index_cs [-a bwtsw|div|is] [-p prefix] <in.fasta>\n");
+    return 1;
+  }
+  if (prefix.empty()) prefix = argv[optind];
+  Packed nt, cs;
+  if (!fa2pac(argv[optind], prefix + ".nt", nt)) return 1;  // bwtindex.c:87-90
+  ibwa_ctx_t *ctx = nullptr;
+  if (ibwa_ctx_create(0, &ctx)) return die("ibwa_ctx_create");
+  int rc = pac2cspac(ctx, prefix + ".nt", prefix, &cs);  // :93-100
+  if (!rc && !pac_rev(prefix + ".pac", prefix + ".rpac")) {
+    fprintf(stderr, "[ibwa-amd index_cs] cannot write %s.rpac\n", prefix.c_str());
+    rc = 1;
+  }
+  if (!rc) rc = build_bwt_sa(ctx, prefix, cs);
   ibwa_ctx_destroy(ctx);
-  return 0;
+  return rc;
 }

@@ -332,6 +332,10 @@ struct Dbs {
   std::vector<RefDb> db;
   uint64_t l_pac = 0;  // sum of the references' l_pac
   bool pac_on_device = false;  // the engine contexts hold the set's sequence: refine_gapped runs on the device
+  // a colour-space set (dbset.c:144, the .sai header's mode lacks COMPREAD): `db` holds the colour
+  // sequences and nt the nucleotide ones (dbs->ntbns, <prefix>.nt of every reference, same offsets)
+  bool color_space = false;
+  std::unique_ptr<Dbs> nt;
   // coord2idx (dbset.c:17-39)
   int coord2idx(int64_t pos) const {
     const int count = (int)db.size();
@@ -885,6 +889,9 @@ struct Refine {
   int dbidx = 0, seqid = -1;  // the hit's reference and (remapped references) its sequence
   Read *s = nullptr;
   Multi *q = nullptr;  // null: the read's own hit
+  // is_end_correct (bwase.c:163-166): pos + len is the hit's end on the forward strand; false only for
+  // the second pass over colour-converted reads, where pos itself is right
+  bool end_correct = true;
 };
 
 // the window of one refinement (dbset_extract_remapped on a remapped reference); fills the
@@ -897,7 +904,7 @@ inline bool refine_prepare(const Dbs &b, Read &s, uint64_t pos, int ext, Refine 
   if (ext > 0) {
     ref_start = p;
   } else {
-    const int64_t x = p + s.len;  // is_end_correct = 1
+    const int64_t x = p + (j.end_correct ? s.len : ref_len);  // bwase.c:189
     ref_start = x - ref_len > 0 ? x - ref_len : 0;
     ref_len = x - ref_start;
   }
@@ -919,7 +926,7 @@ inline void refine_finish(const Dbs &b, const Refine &j, const uint32_t *c32, in
   cigar.clear();
   for (int k = 0; k < n32; ++k) cigar.push_back(cig_make(c32[k] & 0xf, c32[k] >> 4));  // bwa_aln_path2cigar
   int64_t p = (int64_t)*pos;
-  if (j.ext < 0) {  // is_end_correct: fix the coordinate of a forward-strand read
+  if (j.ext < 0 && j.end_correct) {  // fix the coordinate of a forward-strand read (bwase.c:201)
     int64_t l = 0;
     for (uint32_t c : cigar) {
       if (cig_op(c) == FROM_D) l -= cig_len(c);
@@ -951,8 +958,11 @@ inline void refine_finish(const Dbs &b, const Refine &j, const uint32_t *c32, in
 // 0.2-0.25 s slower per command than the host threads), IBWA_REFINE_HOST=1 overrides it,
 // and no reference of the set has a remap table (their windows come from extract_remapped and their
 // CIGARs go through translate_cigar, which stay on the host).  The CLI then loads the set's .pac
-// bytes onto its engine context(s) and sets Dbs::pac_on_device.
+// bytes onto its engine context(s) and sets Dbs::pac_on_device.  A colour-space set always takes the
+// host path (IBWA_REFINE_DEVICE is ignored for it): its second pass over the nucleotide sequences
+// (refine_color) is built on the host path's stages.
 inline bool refine_wants_device(const Dbs &b) {
+  if (b.color_space) return false;
   auto on = [](const char *name) {
     const char *e = getenv(name);
     return e && *e && strcmp(e, "0");
@@ -1100,12 +1110,13 @@ inline int refine_gapped_device(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read 
   return 0;
 }
 
-// bwa_refine_gapped (bwase.c:333-416) over a set of reads: the banded global alignment of every
-// gapped hit (refine_gapped_core, bwase.c:167-241) in one ibwa_global_batch launch, then MD/NM at
-// each read's remapped_pos as the reference has it at that point (bwase.c:401) and the
-// trimmed-read correction.  Returns 0, 1 on a bad position (message printed), -1 on a GPU error.
-inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads) {
-  if (b.pac_on_device) return refine_gapped_device(ctx, b, reads);
+// One pass of refine_gapped_core (bwase.c:167-241) over a set of reads, the windows from the sequences
+// of b, in one ibwa_global_batch launch.  second == false: the first pass of bwa_refine_gapped
+// (bwase.c:339-365, is_end_correct = 1).  second == true: the pass over colour-converted reads
+// (:373-386, is_end_correct = 0; b is the nucleotide set): every gapped multi hit with the read's own
+// remapped_seqid, and the read's own hit where it has a CIGAR.  Returns 0, 1 on a bad position
+// (message printed), -1 on a GPU error.
+inline int refine_pass(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads, bool second) {
   // the jobs in read order, gathered in contiguous read ranges on the host threads and concatenated
   struct Part {
     std::vector<Refine> jobs;
@@ -1125,6 +1136,7 @@ inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &rea
       j.q = q;
       j.dbidx = dbidx;
       j.seqid = seqid;
+      j.end_correct = !second;
       if (ps > b.l_pac) {
         P.bad_pos = ps;
         return false;
@@ -1147,9 +1159,11 @@ inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &rea
       bool ok = true;
       for (Multi &q : p.multi) {  // bwt_multi1_t.dbidx / remapped_seqid are 0 (select_sai_multi)
         if (q.gap == 0) continue;
-        if (!(ok = add_job(p, &q, q.pos, (q.strand ? 1 : -1) * q.gap, q.strand, 0, 0))) break;
+        if (!(ok = add_job(p, &q, q.pos, (q.strand ? 1 : -1) * q.gap, q.strand, 0, second ? p.remapped_seqid : 0))) break;
       }
-      if (ok && !(p.type == TYPE_NO_MATCH || p.type == TYPE_MATESW || (p.n_gapo == 0 && remapped_gapo == 0)))
+      const bool own = second ? p.type != TYPE_NO_MATCH && p.has_cigar
+                              : !(p.type == TYPE_NO_MATCH || p.type == TYPE_MATESW || (p.n_gapo == 0 && remapped_gapo == 0));
+      if (ok && own)
         ok = add_job(p, nullptr, p.pos, (p.strand ? 1 : -1) * (p.n_gapo + p.n_gape), p.strand, p.dbidx, p.remapped_seqid);
       if (!ok) P.bad = i;
     }
@@ -1197,18 +1211,139 @@ inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &rea
     });
     ibwa_free(c32);
   }
+  return 0;
+}
+
+// bwa_refine_gapped's colour branch (bwase.c:367-388) after the first pass: bwa_cs2nt_core
+// (cs2nt.c:113-196) of every mapped read -- rows, decode and qualities in one ibwa_cs2nt_batch over the
+// resident nucleotide sequence, then the host updates of cs2nt.c:177-194 -- and the second refinement
+// pass against the nucleotide set.  Returns as refine_pass.
+inline int refine_color(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads) {
+  std::vector<Read *> who;
+  for (Read *p : reads)
+    if (p->type != TYPE_NO_MATCH) who.push_back(p);
+  const int64_t n = (int64_t)who.size();
+  if (n > 0) {
+    std::vector<uint64_t> pos(n), off(n + 1, 0), coff(n + 1, 0);
+    std::vector<uint32_t> len(n), new_len(n);
+    std::vector<int32_t> nc(n);
+    std::vector<uint8_t> strand(n);
+    for (int64_t j = 0; j < n; ++j) {
+      const Read &p = *who[j];
+      if (!p.has_qual || (int)p.qual.size() < p.len) {
+        fprintf(stderr, "[bwa_cs2nt_core] read %s has no qualities: colour-space reads need them\n", p.name.c_str());
+        return 1;
+      }
+      off[j + 1] = off[j] + (uint64_t)p.len;
+      coff[j + 1] = coff[j] + (p.has_cigar ? p.cigar.size() : 0);
+    }
+    std::vector<uint8_t> sbuf(off[n] + 1), qbuf(off[n] + 1), obuf(off[n] + 1);
+    std::vector<uint32_t> cbuf(coff[n] + 1);
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t j = lo; j < hi; ++j) {
+        const Read &p = *who[j];
+        pos[j] = p.pos;
+        strand[j] = (uint8_t)(p.strand != 0);
+        len[j] = (uint32_t)p.len;
+        nc[j] = p.has_cigar ? (int32_t)p.cigar.size() : 0;
+        memcpy(sbuf.data() + off[j], p.strand ? p.rseq.data() : p.seq.data(), (size_t)p.len);
+        memcpy(qbuf.data() + off[j], p.qual.data(), (size_t)p.len);
+        if (nc[j]) memcpy(cbuf.data() + coff[j], p.cigar.data(), p.cigar.size() * 4);
+      }
+    });
+    if (ibwa_cs2nt_batch(ctx, n, pos.data(), strand.data(), sbuf.data(), qbuf.data(), off.data(), len.data(), nc.data(),
+                         cbuf.data(), obuf.data(), new_len.data()))
+      return -1;
+    // update p (cs2nt.c:177-194): the decoded bases into the hit's strand array, the other strand's by
+    // reverse complement, the quality string (reversed back for strand 1)
+    parallel_chunks(n, [&](int64_t lo, int64_t hi, int) {
+      for (int64_t j = lo; j < hi; ++j) {
+        Read &p = *who[j];
+        const int l = (int)new_len[j];
+        const uint8_t *o = obuf.data() + off[j];
+        std::vector<uint8_t> &sq = p.strand ? p.rseq : p.seq, &other = p.strand ? p.seq : p.rseq;
+        p.len = p.full_len = l;
+        sq.resize((size_t)l);
+        other.resize((size_t)l);
+        p.qual.resize((size_t)l);
+        for (int i = 0; i < l; ++i) {
+          p.qual[i] = (char)((o[i] & 0x3f) + 33);
+          sq[i] = o[i] >> 6;
+        }
+        for (int i = 0; i < l; ++i) other[i] = 3 - sq[l - 1 - i];
+        if (p.strand) std::reverse(p.qual.begin(), p.qual.end());
+      }
+    });
+  }
+  return refine_pass(ctx, *b.nt, reads, true);
+}
+
+// bwa_refine_gapped (bwase.c:333-416) over a set of reads: the banded global alignment of every
+// gapped hit (refine_pass), for a colour-space set the conversion to nucleotides and the second pass
+// (refine_color), then MD/NM at each read's remapped_pos as the reference has it at that point
+// (bwase.c:401; against the nucleotide sequences for a colour-space set) and the trimmed-read
+// correction (not for colour space, :410).  Returns 0, 1 on a bad position or read (message
+// printed), -1 on a GPU error.
+inline int refine_gapped(ibwa_ctx_t *ctx, const Dbs &b, std::vector<Read *> &reads) {
+  if (b.pac_on_device) return refine_gapped_device(ctx, b, reads);
+  if (int rc = refine_pass(ctx, b, reads, false)) return rc;
+  if (b.color_space)
+    if (int rc = refine_color(ctx, b, reads)) return rc;
+  const Dbs &mdset = b.color_space ? *b.nt : b;
   parallel_chunks((int64_t)reads.size(), [&](int64_t lo, int64_t hi, int) {
     for (int64_t t = lo; t < hi; ++t) {
       Read &p = *reads[t];
       if (p.type != TYPE_NO_MATCH) {
-        p.md = cal_md1(p, p.remapped_pos, p.strand ? p.rseq.data() : p.seq.data(), b, &p.nm);
+        p.md = cal_md1(p, p.remapped_pos, p.strand ? p.rseq.data() : p.seq.data(), mdset, &p.nm);
         p.nm &= 0xfff;
         p.has_md = true;
       }
-      correct_trimmed(p);
+      if (!b.color_space) correct_trimmed(p);
     }
   });
   return 0;
+}
+
+// The nucleotide side of a colour-space set: <prefix>.nt (.ann, .amb, .pac) of every reference
+// (seq_restore(prefix, ".nt"), dbset.c:161-165) at the colour references' offsets.  A missing file is
+// named; a reference with a remap table is refused (dbset_extract_remapped over ntbns is not built).
+inline bool restore_nt_set(const std::vector<std::string> &prefixes, Dbs &d, const char *who) {
+  for (const RefDb &r : d.db)
+    if (r.remap > 0) {
+      fprintf(stderr, "[%s] a color-space set in which a reference has a remap table is not supported\n", who);
+      return false;
+    }
+  d.nt.reset(new Dbs);
+  d.nt->db.resize(d.db.size());
+  for (size_t i = 0; i < d.db.size(); ++i) {
+    const std::string pre = prefixes[i] + ".nt";
+    for (const char *ext : {".ann", ".amb", ".pac"}) {
+      FILE *fp = fopen((pre + ext).c_str(), "rb");
+      if (!fp) {
+        fprintf(stderr, "[%s] color-space alignments need the nucleotide sequences: cannot open %s%s\n", who, pre.c_str(), ext);
+        return false;
+      }
+      fclose(fp);
+    }
+    RefDb &r = d.nt->db[i];
+    if (!bns_restore(pre, r.bns) || r.bns.l_pac != d.db[i].bns.l_pac) {
+      fprintf(stderr, "[%s] %s.ann / .amb / .pac do not match %s\n", who, pre.c_str(), prefixes[i].c_str());
+      return false;
+    }
+    r.offset = d.nt->l_pac;
+    d.nt->l_pac += (uint64_t)r.bns.l_pac;
+  }
+  return true;
+}
+// the nucleotide sequences onto ctx (ibwa_ctx_load_ntpac); false on an error
+inline bool load_ntpac_to_device(ibwa_ctx_t *ctx, const Dbs &b) {
+  std::vector<const uint8_t *> pacs;
+  std::vector<uint64_t> lens;
+  for (const RefDb &r : b.nt->db) {
+    pacs.push_back(r.bns.pac.data());
+    lens.push_back((uint64_t)r.bns.l_pac);
+  }
+  return ibwa_ctx_load_ntpac(ctx, (int)pacs.size(), pacs.data(), lens.data()) == 0;
 }
 
 // ---------------------------------------------------------------- SAM output (bwa_print_sam1, bwase.c:451-581)

@@ -31,6 +31,11 @@
 // wide interval (whose strand and read length the cached positions keep) -- or waited for: a batch
 // whose insert size cannot be inferred takes the previous batch's (bwape.c:410-411), and the SAM is
 // written batch by batch in file order.  The output does not depend on N.
+//
+// Colour-space .sai files (aln -c: the second end's header lacks COMPREAD, dbset.c:144) restore
+// <prefix>.nt of every reference beside the colour index, resident once per device, and run
+// bwa_refine_gapped's colour branch (bwase.c:367-388; sam_common.h refine_color) on both ends, mate
+// rescues with their CIGARs included.  A colour set with a remap table is refused.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -1626,10 +1631,6 @@ int sampe_main(int argc, char *argv[]) {
       }
       S.fp_sai[j].push_back(fp);
     }
-    if (!(S.gopt[j].mode & IBWA_MODE_COMPREAD)) {
-      fprintf(stderr, "[ibwa-amd sampe] color-space alignments (aln -c) need the .nt index: not supported\n");
-      return 1;
-    }
   }
   for (int j = 0; j < 2; ++j) {
     if (!src[j].open(fq[j], S.gopt[j])) {
@@ -1695,6 +1696,15 @@ int sampe_main(int argc, char *argv[]) {
   // other workers borrow it with the index
   bool host_all = true;
   for (int d = 0; d < count; ++d) host_all = host_all && host_ok[d] >= 1;
+  // a colour-space set (dbset.c:144, the mode of the second end's header as dbset_restore gets it,
+  // bwape.c:470): the nucleotide sequences beside the colour ones, resident on each device for
+  // bwa_cs2nt_core's rows, before the other workers borrow them with the index
+  S.dbs.color_space = !(S.gopt[1].mode & IBWA_MODE_COMPREAD);
+  if (!gpu_rc && host_all && S.dbs.color_space) {
+    if (!restore_nt_set(prefixes, S.dbs, "ibwa-amd sampe")) return 1;
+    for (int w = 0; w < n_load && !gpu_rc; ++w)
+      if (!load_ntpac_to_device(S.W[w].ctx[0], S.dbs)) gpu_rc = 7;
+  }
   if (!gpu_rc && host_all && refine_wants_device(S.dbs)) {
     S.W[0].ph.mark("load index (first batch read meanwhile)");
     for (int w = 0; w < n_load && !gpu_rc; ++w)
@@ -1710,6 +1720,7 @@ int sampe_main(int argc, char *argv[]) {
       if (ibwa_ctx_share_index(cx, S.W[w % n_dev].ctx[d])) gpu_rc = 5;
     }
   if (gpu_rc == 6) return die("load .pac to the device");
+  if (gpu_rc == 7) return die("load .nt.pac to the device");
   if (gpu_rc == 1) return die("ibwa_ctx_create");
   if (gpu_rc == 2) return die("load .bwt / .rbwt");
   if (gpu_rc == 3) return die("load .sa / .rsa");

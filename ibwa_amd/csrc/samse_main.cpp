@@ -11,7 +11,9 @@
 // correction (:297-331) and bwa_print_sam1 (:451-581).  Reference quirks are kept: samse
 // never sets remapped_pos, so MD/NM are computed at pac position 0 (bwase.c:401) and every
 // mapped read carries a ZR tag (bwase.c:556-563).  Color-space input (.sai written with -c)
-// needs the .nt index and is rejected.
+// restores <prefix>.nt beside the colour index and runs bwa_refine_gapped's colour branch
+// (bwase.c:367-388): bwa_cs2nt_core on the GPU (ibwa_cs2nt_batch), then the second refinement pass
+// and MD/NM against the nucleotide sequences (sam_common.h refine_color).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -63,6 +65,13 @@ int run_samse(Reader &rd, FILE *fp_sa, const ibwa_gap_opt_t &opt, const std::str
     return 1;
   }
   dbs.l_pac = (uint64_t)b.l_pac;
+  // a colour-space .sai (dbset.c:144): the nucleotide sequences beside the colour ones, resident for
+  // bwa_cs2nt_core's rows
+  dbs.color_space = !(opt.mode & IBWA_MODE_COMPREAD);
+  if (dbs.color_space) {
+    if (!restore_nt_set({prefix}, dbs, "ibwa-amd samse")) return 1;
+    if (!load_ntpac_to_device(ctx, dbs)) return die("load .nt.pac to the device");
+  }
   // the packed reference onto the device: bwa_refine_gapped's windows and MD/NM read it there
   ph.mark("load index");
   if (refine_wants_device(dbs)) {
@@ -187,10 +196,6 @@ int samse_main(int argc, char *argv[]) {
   ibwa_gap_opt_t opt;
   if (fread(&opt, sizeof opt, 1, fp_sa) != 1) {
     fprintf(stderr, "[ibwa-amd samse] %s: no .sai header\n", argv[optind + 1]);
-    return 1;
-  }
-  if (!(opt.mode & IBWA_MODE_COMPREAD)) {
-    fprintf(stderr, "[ibwa-amd samse] color-space alignments (aln -c) need the .nt index: not supported\n");
     return 1;
   }
   FILE *out = fn_out ? fopen(fn_out, "w") : stdout;

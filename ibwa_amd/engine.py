@@ -139,6 +139,10 @@ CAPI = {
     "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
     "ibwa_md_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(c.c_void_p)]),
+    "ibwa_pac2cspac": (_i, [_vp, _vp, _u64, _vp]),
+    "ibwa_ctx_load_ntpac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
+    "ibwa_cs2nt_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_cs2nt_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -570,6 +574,64 @@ class Engine:
         if raw:
             return offs, text, nm
         return [text[int(offs[i]):int(offs[i + 1]) - 1].decode() for i in range(n)], nm
+
+    def pac2cspac(self, nt_pac, l_pac):
+        """bwa_pac2cspac_core (ibwa_pac2cspac): a nucleotide .pac's bytes -> the l_pac // 4 + 1 colour bytes."""
+        src = np.zeros((int(l_pac) + 3) // 4, np.uint8)
+        have = np.frombuffer(bytes(nt_pac), np.uint8)[:src.size]
+        src[:have.size] = have
+        out = np.zeros(int(l_pac) // 4 + 1, np.uint8)
+        _chk(lib().ibwa_pac2cspac(self.h, src.ctypes.data, int(l_pac), out.ctypes.data))
+        return out
+
+    def load_ntpac(self, pacs, l_pacs):
+        """The nucleotide sequences of a colour-space set (their .nt.pac bytes and l_pac) onto the device
+        (ibwa_ctx_load_ntpac)."""
+        keep = [np.ascontiguousarray(np.frombuffer(bytes(p), np.uint8) if not isinstance(p, np.ndarray) else p,
+                                     dtype=np.uint8) for p in pacs]
+        ptrs = (c.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
+        ls = (c.c_uint64 * len(keep))(*[int(x) for x in l_pacs])
+        _chk(lib().ibwa_ctx_load_ntpac(self.h, len(keep), ptrs, ls))
+
+    def cs2nt_rows(self, nt_refs, cs_reads):
+        """cs2nt_DP + cs2nt_nt_qual per row pair (ibwa_cs2nt_rows): nt_refs[i] has len(cs_reads[i]) + 1 codes
+        -> list of uint8 arrays of len(cs_reads[i]) - 1 bytes, base << 6 | qual."""
+        n = len(cs_reads)
+        size = np.array([len(x) for x in cs_reads], np.uint32)
+        assert all(len(r) == int(s) + 1 for r, s in zip(nt_refs, size))
+        off = np.zeros(n + 1, np.uint64)
+        off[1:] = np.cumsum(size.astype(np.uint64) + 1)
+        ref = np.zeros(int(off[n]) + 1, np.uint8)
+        cs = np.zeros(int(off[n]) + 1, np.uint8)
+        for i in range(n):
+            o = int(off[i])
+            ref[o:o + int(size[i]) + 1] = nt_refs[i]
+            cs[o:o + int(size[i])] = cs_reads[i]
+        out = np.full(int(off[n]) + 1, 0xFF, np.uint8)
+        _chk(lib().ibwa_cs2nt_rows(self.h, n, ref.ctypes.data, cs.ctypes.data, off.ctypes.data, size.ctypes.data,
+                                   out.ctypes.data, off.ctypes.data))
+        return [out[int(off[i]):int(off[i]) + int(size[i]) - 1].copy() for i in range(n)]
+
+    def cs2nt(self, pos, strand, seqs, quals, cigars=None):
+        """bwa_cs2nt_core's rows from the resident nucleotide sequence, then the DP (ibwa_cs2nt_batch).
+        seqs[i]: colour codes in the hit's orientation; quals[i]: the quality string as read (bytes);
+        cigars: None, or per read None / a bwa_cigar_t sequence -> list of uint8 arrays, base << 6 | qual."""
+        n = len(seqs)
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        strand = np.ascontiguousarray(strand, dtype=np.uint8)
+        s, off, ln = self._pack_reads(seqs)
+        q, _, lq = self._pack_reads([np.frombuffer(bytes(x), np.uint8) for x in quals])
+        assert (ln == lq).all()
+        nc = cg = None
+        if cigars is not None:
+            nc = np.array([0 if x is None else len(x) for x in cigars], np.int32)
+            cg = np.concatenate([np.asarray(x, np.uint32) for x in cigars if x is not None] + [np.zeros(1, np.uint32)])
+        out = np.full(s.size, 0xFF, np.uint8)
+        new_len = np.zeros(n, np.uint32)
+        _chk(lib().ibwa_cs2nt_batch(self.h, n, pos.ctypes.data, strand.ctypes.data, s.ctypes.data, q.ctypes.data,
+                                    off.ctypes.data, ln.ctypes.data, nc.ctypes.data if nc is not None else None,
+                                    cg.ctypes.data if cg is not None else None, out.ctypes.data, new_len.ctypes.data))
+        return [out[int(off[i]):int(off[i]) + int(new_len[i])].copy() for i in range(n)]
 
     def occ4(self, strand, ks):
         ks = np.ascontiguousarray(ks, dtype=np.uint32)

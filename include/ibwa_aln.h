@@ -446,6 +446,45 @@ int ibwa_md_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const uint8_t
                   const uint32_t *len, const int32_t *n_cigar, const uint32_t *cigar, int32_t *nm, uint64_t **md_off,
                   const char **md);
 
+/*
+ * Colour space: the colour sequence of a nucleotide .pac, and bwa_cs2nt_core (cs2nt.c:113-196), which
+ * turns the colours of a mapped read into bases and base qualities.
+ *
+ * ibwa_pac2cspac: bwa_pac2cspac_core (bwtmisc.c:202-219).  nt_pac: (l_pac + 3) / 4 bytes of a
+ * nucleotide .pac; cs_pac_out: l_pac / 4 + 1 bytes, what bwa_pac2cspac writes before the count byte
+ * (bwtmisc.c:239).  Symbol 0 is base 0, colour i is nst_color_space_table of bases i - 1 and i; every
+ * bit past l_pac is 0.  Needs no index.
+ *
+ * ibwa_ctx_load_ntpac: the second sequence set of a colour-space dbset (dbs->ntbns, <prefix>.nt.pac of
+ * every reference; dbset.c:144), resident beside ibwa_ctx_load_pac's in the same layout.  Lent by
+ * ibwa_ctx_share_index; refused (IBWA_EINVAL) by a context that borrows or lends its index.
+ *
+ * ibwa_cs2nt_rows: cs2nt_DP (cs2nt.c:37-78) then cs2nt_nt_qual (:84-110) on n caller-built row pairs.
+ * Job i: nt_ref[off[i] .. off[i] + size[i]] (size + 1 codes 0-4) and cs_read[off[i] .. off[i] +
+ * size[i]) (colour << 6 | qual, qual == 63 for an N colour); out[out_off[i] .. + size[i] - 1) gets
+ * cs2nt_nt_qual's result, base << 6 | qual.  size[i] == 0 is IBWA_EINVAL (the reference's loop does
+ * not end there).  Needs no index.
+ *
+ * ibwa_cs2nt_batch: the row construction of bwa_cs2nt_core (cs2nt.c:136-171) from the resident
+ * nucleotide sequence, then the same two functions, for n mapped reads.  Read i: the hit position
+ * pos[i], strand[i], its colour codes seq[off[i] .. + len[i]) in the hit's orientation (p->strand ?
+ * p->rseq : p->seq), its quality string qual[off[i] .. + len[i]) as read (ASCII, + 33; indexed
+ * len - 1 - j on strand 1 as __gen_csbase does), and n_cigar[i] bwa_cigar_t's taken in read order from
+ * `cigar` (<= 0: none; n_cigar == NULL: no read has one).  out[off[i] .. + new_len[i]) gets the
+ * decoded base << 6 | qual bytes and new_len[i] = rows - 1, the read's new length (cs2nt.c:177); the
+ * host updates of cs2nt.c:178-194 are the caller's.  A reference base at or past l_pac is not
+ * defined by the reference (its buffer is uninitialised there): it counts as 4, no base known.
+ * IBWA_ENOINDEX while no nucleotide sequence is loaded; IBWA_EINVAL for a CIGAR that consumes more
+ * colours than the read has or no colour at all.
+ */
+int ibwa_pac2cspac(ibwa_ctx_t *ctx, const uint8_t *nt_pac, uint64_t l_pac, uint8_t *cs_pac_out);
+int ibwa_ctx_load_ntpac(ibwa_ctx_t *ctx, int n_db, const uint8_t *const *pac, const uint64_t *l_pac);
+int ibwa_cs2nt_rows(ibwa_ctx_t *ctx, int64_t n, const uint8_t *nt_ref, const uint8_t *cs_read, const uint64_t *off,
+                    const uint32_t *size, uint8_t *out, const uint64_t *out_off);
+int ibwa_cs2nt_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const uint8_t *strand, const uint8_t *seq,
+                     const uint8_t *qual, const uint64_t *off, const uint32_t *len, const int32_t *n_cigar,
+                     const uint32_t *cigar, uint8_t *out, uint32_t *new_len);
+
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
 
