@@ -21,8 +21,6 @@ namespace ibwa {
 
 namespace {
 
-constexpr int MODE_GAPE = 0x01, MODE_COMPREAD = 0x02, MODE_LOGGAP = 0x04, MODE_NONSTOP = 0x10;
-constexpr int STATE_M = 0, STATE_I = 1, STATE_D = 2;
 
 // All six 16 B loads of a rank-query pair are issued unconditionally so that
 // the compiler can put every fetch of a step in flight before the first wait.
@@ -418,10 +416,6 @@ __global__ void __launch_bounds__(256) k_width(AlnArgs A) {
   if (L > A.o.seed_len)
     width_pair(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, nullptr, nullptr, 0, 4,
                nullptr, sa0, sa1, tx0, tx1, A.ltab[0], A.ltab[1], tdep);
-}
-
-__device__ __forceinline__ int int_log2(uint32_t v) {  // bwtgap.c:93-102
-  return v ? 31 - __builtin_clz(v) : 0;
 }
 
 // bwt_match_exact_alt (bwt.c:235-250) over str[0..i-1] from (k, l)

@@ -455,7 +455,7 @@ int run_aln(std::vector<AlnInput<Reader>> &ins, const std::string &prefix, int n
   if (ibwa_device_count(&n_dev) || n_dev < 1) return die("no HIP device");
   if (n_gpus > n_dev)
     fprintf(stderr, "[ibwa-amd aln] -G %d on %d visible device(s): slice g runs on device g mod %d\n", n_gpus, n_dev, n_dev);
-  // One device arena per GPU, reserved before anything else is allocated (engine.hip Arena): every
+  // One device arena per GPU, reserved before anything else is allocated (arena.h Arena): every
   // buffer -- index, ingest slots, the lanes' search scratch -- is carved from it, so no allocation
   // in the middle of the alignment waits for the driver to wipe memory a previous process released.
   // IBWA_ARENA_GB: its size per GPU (0: none); default: the free memory less a margin, at most

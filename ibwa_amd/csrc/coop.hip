@@ -57,8 +57,6 @@ namespace ibwa {
 
 namespace {
 
-constexpr int MODE_GAPE = 0x01, MODE_COMPREAD = 0x02, MODE_LOGGAP = 0x04, MODE_NONSTOP = 0x10;
-constexpr int STATE_M = 0, STATE_I = 1, STATE_D = 2;
 // Gap group: a gap-opening expansion stages its insertion child with its deletion children pending
 // (ldp field = their symbols; the group's ldp is its i) as one entry in STATE_G.  95 % of gap-open
 // children on a GRCh37-sized genome are never popped, so the deletions are spelled out only when
@@ -74,34 +72,6 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int L_IDLE = 0, L_FETCH = 1, L_EXP = 2, L_TAIL = 3;
 // prologue chain records: the root chain ended in a hit / did not run (read not for this kernel)
 constexpr uint32_t PRO_HIT = 1, PRO_SKIP = 2;
-
-struct Blk {
-  uint4 v0, v1, v2, v3;
-};
-
-__device__ __forceinline__ void load_blk(const uint4 *o, uint32_t row, bool run, Blk &b) {
-  if (run) {
-    const uint4 *p = o + (size_t)(row >> 6) * 4;
-    b.v0 = p[0];
-    b.v1 = p[1];
-    b.v2 = p[2];
-    b.v3 = p[3];
-  }
-}
-
-__device__ __forceinline__ uint32_t occ_of(const uint4 &v, uint32_t row) {
-  const uint32_t o = row & 63;
-  const uint32_t mlo = o >= 31 ? 0xFFFFFFFFu : ((2u << o) - 1u);
-  const uint32_t mhi = o < 32 ? 0u : (o == 63 ? 0xFFFFFFFFu : ((2u << (o - 32)) - 1u));
-  return v.x + (uint32_t)__builtin_popcount(v.z & mlo) + (uint32_t)__builtin_popcount(v.w & mhi);
-}
-
-__device__ __forceinline__ uint32_t pick4(uint4 v, uint32_t c) {
-  const uint32_t lo = (c & 1) ? v.y : v.x, hi = (c & 1) ? v.w : v.z;
-  return (c & 2) ? hi : lo;
-}
-
-__device__ __forceinline__ int int_log2(uint32_t v) { return v ? 31 - __builtin_clz(v) : 0; }
 
 // wave-wide exclusive prefix sum and total (64 lanes, all active): DPP row shifts within the rows
 // of 16 lanes, then the row broadcasts of lanes 15 and 31 -- six VALU steps instead of six

@@ -12,7 +12,7 @@ constexpr uint32_t ST_ALN_OVERFLOW = 2u;    // per-read hit slots exceeded      
 constexpr uint32_t ST_BAD_SCORE = 4u;       // score outside [0, n_stacks): invalid options
 constexpr uint32_t ST_HEAVY = 8u;           // iteration budget of the first pass exceeded -> retry pass
 
-// The engine's device counters: 64-bit slots of one small buffer (engine.hip, ibwa_ctx::d_counter).
+// The engine's device counters: 64-bit slots of one small buffer (engine_ctx.h, ibwa_ctx::d_counter).
 enum CounterSlot {
   CTR_CLAIM = 0,        // a persistent launch's claim counter (every launcher zeroes it)
   CTR_STREAM = 1,       // hit-stream fill (GapArgs / CoopArgs::aln_next; zeroed once per batch)
@@ -21,7 +21,7 @@ enum CounterSlot {
   CTR_RESUMED = 5,      // count of select_resumed
   CTR_TAIL_JUMPS = 7,   // GapArgs::tail_jumps
 };
-// The cooperative launches' bump pointers share another (ibwa_ctx::c_next): a u32 and, past it, a u64.
+// The cooperative launches' bump pointers share another (ibwa_ctx::coop.c_next): a u32 and, past it, a u64.
 enum CoopNextSlot {
   CNEXT_POOL = 0,    // CoopArgs::pool_next, u32 index
   CNEXT_PSTORE = 1,  // CoopArgs::pstore_next, u64 index
@@ -37,6 +37,9 @@ struct AlnOpt {
   int max_gape, max_seed_diff, seed_len, max_top2;
   int n_stacks;   // gap_init_stack size (bwtgap.c:18)
 };
+// AlnOpt::mode bits (BWA_MODE_*, bwtaln.h) and the search states of an entry (bwtgap.c:7-9)
+constexpr int MODE_GAPE = 0x01, MODE_COMPREAD = 0x02, MODE_LOGGAP = 0x04, MODE_NONSTOP = 0x10;
+constexpr int STATE_M = 0, STATE_I = 1, STATE_D = 2;
 
 struct AlnArgs {
   IndexView ix[2];           // ix[0] = .bwt, ix[1] = .rbwt

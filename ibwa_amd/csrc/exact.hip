@@ -32,7 +32,6 @@ namespace ibwa {
 
 namespace {
 
-constexpr int MODE_COMPREAD = 0x02;
 constexpr int EXACT_CHUNK = 512;
 
 // Record of read r at rec + r * stride (uint4 units):
@@ -130,19 +129,12 @@ __device__ __forceinline__ uint4 load64(const uint4 *o, uint32_t row, uint32_t c
   return v;
 }
 
-__device__ __forceinline__ uint32_t occ64(const uint4 &v, uint32_t row) {
-  const uint32_t o = row & 63;
-  const uint32_t mlo = o >= 31 ? 0xFFFFFFFFu : ((2u << o) - 1u);
-  const uint32_t mhi = o < 32 ? 0u : (o == 63 ? 0xFFFFFFFFu : ((2u << (o - 32)) - 1u));
-  return v.x + (uint32_t)__builtin_popcount(v.z & mlo) + (uint32_t)__builtin_popcount(v.w & mhi);
-}
-
 // bwt_2occ + the interval update of bwt_match_exact_alt (bwt.c:243-245);
 // `vk` is the k-1 end's block, or a copy of `vl` when both ends share it
 __device__ __forceinline__ void extend64(const IndexView &ix, uint32_t &k, uint32_t &l, uint32_t c, const uint4 &vk,
                                          const uint4 &vl) {
-  const uint32_t ok = k == 0 ? 0u : occ64(vk, k - 1);
-  const uint32_t ol = occ64(vl, l);
+  const uint32_t ok = k == 0 ? 0u : occ_of(vk, k - 1);
+  const uint32_t ol = occ_of(vl, l);
   const uint32_t base = l2of(ix, c);
   k = base + ok + 1;
   l = base + ol;

@@ -18,7 +18,7 @@
 //   k_fq_encode  one wavefront per record: the reversed nt4 codes, coalesced stores
 // The host hands the rest of the input, from the first record that is not strict, to the serial
 // kseq-semantics reader, exactly as FastqBulk does; the kept reads of the block stay in HBM and
-// are staged for the search passes device to device (engine.hip ibwa_batch_stage_fq).
+// are staged for the search passes device to device (engine_ingest.hip ibwa_batch_stage_fq).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>

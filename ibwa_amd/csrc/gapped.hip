@@ -50,8 +50,6 @@ namespace ibwa {
 
 namespace {
 
-constexpr int MODE_GAPE = 0x01, MODE_COMPREAD = 0x02, MODE_LOGGAP = 0x04, MODE_NONSTOP = 0x10;
-constexpr int STATE_M = 0, STATE_I = 1, STATE_D = 2;
 // Gap group (first pass): a gap-opening expansion pushes the insertion child and then the non-empty
 // deletion children into one bucket, consecutively (bwtgap.c:221-227), and measured on a
 // GRCh37-sized genome 95 % of them are never popped (they score a gap open above the first hit).
@@ -115,43 +113,6 @@ __device__ __forceinline__ int ring_next(uint32_t m, int from) {
   const uint32_t x = ((m >> r) | (m << (GAP_RING - r))) & ((1u << GAP_RING) - 1u);
   return x ? from + __builtin_ctz(x) : (1 << 30);
 }
-
-// The 64-row bit-plane block (occ64.hip): v[c] = {C[c], 0, P_lo[c], P_hi[c]}.  Four named
-// uint4 members, not an array: an array indexed by a runtime symbol is placed in scratch.
-struct Blk {
-  uint4 v0, v1, v2, v3;
-};
-
-__device__ __forceinline__ void load_blk(const uint4 *o, uint32_t row, bool run, Blk &b) {
-  if (run) {
-    const uint4 *p = o + (size_t)(row >> 6) * 4;
-    b.v0 = p[0];
-    b.v1 = p[1];
-    b.v2 = p[2];
-    b.v3 = p[3];
-  }
-}
-
-__device__ __forceinline__ uint32_t occ_of(const uint4 &v, uint32_t row) {
-  const uint32_t o = row & 63;
-  const uint32_t mlo = o >= 31 ? 0xFFFFFFFFu : ((2u << o) - 1u);
-  const uint32_t mhi = o < 32 ? 0u : (o == 63 ? 0xFFFFFFFFu : ((2u << (o - 32)) - 1u));
-  return v.x + (uint32_t)__builtin_popcount(v.z & mlo) + (uint32_t)__builtin_popcount(v.w & mhi);
-}
-
-// all four Occ(c, row) from a block; pick one by a runtime symbol with scalar selects
-// (a select chain over vector aggregates is lowered to an indexed scratch access)
-__device__ __forceinline__ uint4 occ4_of(const Blk &b, uint32_t row) {
-  return make_uint4(occ_of(b.v0, row), occ_of(b.v1, row), occ_of(b.v2, row), occ_of(b.v3, row));
-}
-
-__device__ __forceinline__ uint32_t pick4(uint4 v, uint32_t c) {
-  const uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
-  const uint32_t lo = (c & 1) ? y : x, hi = (c & 1) ? w : z;
-  return (c & 2) ? hi : lo;
-}
-
-__device__ __forceinline__ int int_log2(uint32_t v) { return v ? 31 - __builtin_clz(v) : 0; }
 
 // Entry packing.  Narrow (first pass): 16-bit slot links, i and last_diff_pos 16 bits each.
 // Wide (retry pass, reads < 4096 bp): 24-bit links, the top 8 bits in z above 12-bit i / ldp.

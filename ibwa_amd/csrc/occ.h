@@ -156,4 +156,46 @@ __device__ __forceinline__ void occ4x2(const IndexView &ix, uint32_t k, uint32_t
   occ4_from(cnt, bl, sb, offl, cl);
 }
 
+// ---- the occ64 layout (occ64.hip): the bit-plane blocks k_gapped, k_coop and k_exact rank on ----
+// Per 64 BWT rows four uint4, one per symbol c: v[c] = {C[c], 0, P_lo[c], P_hi[c]} -- the occurrences
+// of c before the block and a bit per row that holds c.  Occ(c, row) = one count + two popcounts.
+
+// The 64-row block.  Four named uint4 members, not an array: an array indexed by a runtime symbol
+// is placed in scratch.
+struct Blk {
+  uint4 v0, v1, v2, v3;
+};
+
+__device__ __forceinline__ void load_blk(const uint4 *o, uint32_t row, bool run, Blk &b) {
+  if (run) {
+    const uint4 *p = o + (size_t)(row >> 6) * 4;
+    b.v0 = p[0];
+    b.v1 = p[1];
+    b.v2 = p[2];
+    b.v3 = p[3];
+  }
+}
+
+__device__ __forceinline__ uint32_t occ_of(const uint4 &v, uint32_t row) {
+  const uint32_t o = row & 63;
+  const uint32_t mlo = o >= 31 ? 0xFFFFFFFFu : ((2u << o) - 1u);
+  const uint32_t mhi = o < 32 ? 0u : (o == 63 ? 0xFFFFFFFFu : ((2u << (o - 32)) - 1u));
+  return v.x + (uint32_t)__builtin_popcount(v.z & mlo) + (uint32_t)__builtin_popcount(v.w & mhi);
+}
+
+// all four Occ(c, row) from a block; pick one by a runtime symbol with scalar selects
+// (a select chain over vector aggregates is lowered to an indexed scratch access)
+__device__ __forceinline__ uint4 occ4_of(const Blk &b, uint32_t row) {
+  return make_uint4(occ_of(b.v0, row), occ_of(b.v1, row), occ_of(b.v2, row), occ_of(b.v3, row));
+}
+
+__device__ __forceinline__ uint32_t pick4(uint4 v, uint32_t c) {
+  const uint32_t x = v.x, y = v.y, z = v.z, w = v.w;
+  const uint32_t lo = (c & 1) ? y : x, hi = (c & 1) ? w : z;
+  return (c & 2) ? hi : lo;
+}
+
+// int_log2 of bwtgap.c:93-102
+__device__ __forceinline__ int int_log2(uint32_t v) { return v ? 31 - __builtin_clz(v) : 0; }
+
 }  // namespace ibwa

@@ -18,14 +18,23 @@
 //         I <cigar> <exact> <start> <len>          is_remapped_sequence_identical
 //         T <cigar> <start> <read cigar|-> <len>   translate_cigar (read CIGAR as text, - for none)
 //         L <file> <n_seqs>                        load_remappings
+//   host_check arena <threads>
+//       arena.h (the device arena's range allocator) over a 1 MiB host block: a fixed-seed sequence
+//       of 20 000 mixed alloc / release calls of 1 B .. 64 KiB.  One thread: checked call by call
+//       against a granule map (no overlap, inside the block, used / peak, null exactly when no free
+//       range fits).  Several threads: the same sequence from each, over its own handles, on one
+//       arena; every range is filled with its owner's tag and read back before its release.  Both:
+//       after the last release the free list is the one range {0: size}.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
 #include <string>
+#include <thread>
 #include <vector>
 
+#include "arena.h"
 #include "readers.h"
 #include "sam_common.h"
 #include "remap.h"
@@ -62,9 +71,137 @@ int drain(Reader &rd, int mode, int trim) {
   return 0;
 }
 
+constexpr size_t kArenaBytes = 1u << 20, kGranule = 4096, kGranules = kArenaBytes / kGranule;
+constexpr int kArenaCalls = 20000;
+
+struct Rng {  // splitmix64
+  uint64_t s;
+  uint64_t next() {
+    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+  }
+};
+struct Held {
+  char *p;
+  size_t n;  // as asked for
+};
+size_t rounded(size_t n) { return (n + kGranule - 1) & ~(kGranule - 1); }
+
+#define ARENA_CHECK(cond, ...)                 \
+  do {                                         \
+    if (!(cond)) {                             \
+      fprintf(stderr, "arena: " __VA_ARGS__);  \
+      fprintf(stderr, "\n");                   \
+      return 1;                                \
+    }                                          \
+  } while (0)
+
+// the sequence on one thread, every call checked against a map of the block's granules
+int arena_checked(ibwa::Arena &a) {
+  std::vector<char> taken(kGranules, 0);
+  std::vector<Held> live;
+  Rng rng{20261020};
+  size_t used = 0, peak = 0;
+  int n_null = 0, n_ok = 0;
+  for (int call = 0; call < kArenaCalls; ++call) {
+    const bool do_alloc = live.empty() || rng.next() % 100 < 55;
+    if (do_alloc) {
+      const size_t n = 1 + rng.next() % 65536, g = rounded(n) / kGranule;
+      size_t run = 0, best = 0;  // the longest free run of granules
+      for (size_t i = 0; i < kGranules; ++i) {
+        run = taken[i] ? 0 : run + 1;
+        best = std::max(best, run);
+      }
+      char *p = static_cast<char *>(a.alloc(n));
+      ARENA_CHECK((p == nullptr) == (best < g), "call %d: alloc(%zu) %s with a free run of %zu granules", call, n,
+                  p ? "succeeded" : "failed", best);
+      if (!p) {
+        ++n_null;
+        continue;
+      }
+      ++n_ok;
+      ARENA_CHECK(a.owns(p) && p + rounded(n) <= a.base + a.size && (size_t)(p - a.base) % kGranule == 0,
+                  "call %d: range outside the block", call);
+      for (size_t i = (size_t)(p - a.base) / kGranule, e = i + g; i < e; ++i) {
+        ARENA_CHECK(!taken[i], "call %d: granule %zu handed out twice", call, i);
+        taken[i] = 1;
+      }
+      live.push_back({p, n});
+      used += rounded(n);
+      peak = std::max(peak, used);
+    } else {
+      const size_t j = rng.next() % live.size();
+      const Held h = live[j];
+      live[j] = live.back();
+      live.pop_back();
+      a.release(h.p, h.n);
+      for (size_t i = (size_t)(h.p - a.base) / kGranule, e = i + rounded(h.n) / kGranule; i < e; ++i) taken[i] = 0;
+      used -= rounded(h.n);
+    }
+    ARENA_CHECK(a.used == used && a.peak == peak, "call %d: used %zu (expected %zu), peak %zu (expected %zu)", call,
+                a.used, used, a.peak, peak);
+  }
+  ARENA_CHECK(n_null > 0 && n_ok > 0, "the sequence never %s", n_null ? "succeeded" : "filled the block");
+  for (const Held &h : live) a.release(h.p, h.n);
+  return 0;
+}
+
+// the same sequence from one of several threads on a shared arena; *bad: a range's bytes changed under its owner
+void arena_worker(ibwa::Arena &a, int tag, std::atomic<int> *bad) {
+  std::vector<Held> live;
+  Rng rng{20261020};
+  auto give_back = [&](const Held &h) {
+    for (size_t i = 0; i < h.n; ++i)
+      if (h.p[i] != (char)tag) bad->fetch_add(1);
+    a.release(h.p, h.n);
+  };
+  for (int call = 0; call < kArenaCalls; ++call) {
+    if (live.empty() || rng.next() % 100 < 55) {
+      const size_t n = 1 + rng.next() % 65536;
+      char *p = static_cast<char *>(a.alloc(n));
+      if (!p) continue;
+      if (!a.owns(p) || p + rounded(n) > a.base + a.size) bad->fetch_add(1);
+      memset(p, tag, n);
+      live.push_back({p, n});
+    } else {
+      const size_t j = rng.next() % live.size();
+      give_back(live[j]);
+      live[j] = live.back();
+      live.pop_back();
+    }
+  }
+  for (const Held &h : live) give_back(h);
+}
+
+int arena_check(int threads) {
+  std::vector<char> block(kArenaBytes);
+  ibwa::Arena a;
+  a.base = block.data();
+  a.size = kArenaBytes;
+  a.free_[0] = kArenaBytes;
+  if (threads <= 1) {
+    if (int rc = arena_checked(a)) return rc;
+  } else {
+    std::atomic<int> bad{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < threads; ++t) th.emplace_back(arena_worker, std::ref(a), t + 1, &bad);
+    for (auto &x : th) x.join();
+    ARENA_CHECK(bad == 0, "%d ranges outside the block or overwritten by another owner", bad.load());
+    ARENA_CHECK(a.peak <= kArenaBytes, "peak %zu past the block", a.peak);
+  }
+  ARENA_CHECK(a.used == 0, "used %zu after the last release", a.used);
+  ARENA_CHECK(a.free_.size() == 1 && a.free_.begin()->first == 0 && a.free_.begin()->second == kArenaBytes,
+              "free list of %zu ranges after the last release", a.free_.size());
+  printf("ok %d\n", threads);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+  if (argc >= 3 && !strcmp(argv[1], "arena")) return arena_check(atoi(argv[2]));
   init_tables();
   if (argc >= 5 && !strcmp(argv[1], "reads")) {
     const int mode = atoi(argv[3]), trim = atoi(argv[4]);

@@ -111,7 +111,7 @@ def test_hits_inside_wide_levels(golden_dir, tandem_engine, fq, early):
 @pytest.mark.parametrize("argv", [[], ["-n", "3", "-o", "2", "-e", "3"]], ids=["default", "n3o2e3"])
 @pytest.mark.parametrize("fq", ["reads_r100.fq", "reads_mixed.fq"])
 def test_resumed_reads(golden_dir, gpu_engine, fq, argv, iters, early):
-    """The first pass leaves states only when its widths fit in LDS (engine.hip, plan_first_pass: `lw`):
+    """The first pass leaves states only when its widths fit in LDS (engine_aln.hip, plan_first_pass: `lw`):
     at most 6 differences in the batch, and gap_lw_min_waves waves per CU with the batch's longest row.
     reads_mixed.fq reaches 250 bp.  Under -n 3 only the waves stand in the way, so the mixed batches run
     with gap_lw_min_waves 1 and their 200 and 250 bp reads are resumed too.  Under the default options a

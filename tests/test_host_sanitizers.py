@@ -2,7 +2,7 @@
 parsing), sam_common.h (bwa_read_seq / bwa_read_bam record preparation, the Background parser
 thread, parallel_chunks, print_parallel, .ann/.amb/.pac loading), compiled with g++ under
 AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer, driven by
-tests/host/host_check.cpp over the golden inputs and over truncated / corrupt BAM records.
+tests/host/host_check.cpp over the golden inputs and over truncated / corrupt BAM records; arena.h (the device arena's range allocator) the same way.
 CPU only (no HIP code is built here)."""
 import gzip
 import os
@@ -33,7 +33,7 @@ def bins():
     out = {}
     for name, flags in FLAVOURS.items():
         exe = os.path.join(OUT, f"host_check_{name}")
-        deps = [SRC] + [os.path.join(ROOT, "ibwa_amd", "csrc", f) for f in ("readers.h", "sam_common.h", "remap.h")]
+        deps = [SRC] + [os.path.join(ROOT, "ibwa_amd", "csrc", f) for f in ("readers.h", "sam_common.h", "remap.h", "arena.h")]
         if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
             subprocess.run(["g++", "-std=c++17", "-g", "-pthread", *flags, "-I", os.path.join(ROOT, "include"),
                             "-I", os.path.join(ROOT, "ibwa_amd", "csrc"), SRC, "-o", exe, "-lz"], check=True)
@@ -122,6 +122,18 @@ def test_bns_and_chunks(bins):
         for n, t in [(0, 4), (1, 8), (255, 3), (100000, 8), (12345, 0)]:
             r = run(exe, "chunks", n, t)
             assert r.returncode == 0 and r.stdout.startswith(b"ok"), (name, n, t)
+
+
+def test_arena(bins):
+    """arena.h (the device arena's first-fit range allocator, host code only) over a 1 MiB host block:
+    20 000 fixed-seed alloc / release calls of 1 B .. 64 KiB.  One thread: every call checked against
+    a granule map (ranges disjoint and inside the block, `used` the sum of the live rounded sizes,
+    `peak` its running maximum, null exactly when no free range fits).  Four threads, each over its
+    own handles on one arena: no range changes under its owner.  Both end with the free list {0: size}."""
+    for name, exe in bins.items():
+        for threads in (1, 4):
+            r = run(exe, "arena", threads)
+            assert r.returncode == 0 and r.stdout == b"ok %d\n" % threads, (name, r.stdout, r.stderr.decode()[-2000:])
 
 
 def test_remap_known_answers(bins, tmp_path):

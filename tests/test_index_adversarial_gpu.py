@@ -28,7 +28,7 @@ What each text family is aimed at, i.e. where to look when a case fails:
   AC4096, lastG1000       skewed alphabets: L2[c] == L2[c + 1]; a symbol whose only occurrence is
                           the text's last (the first BWT symbol, row 0).
 
-test_builder            -> sa_build.hip (+ k_pack_blocks, export_bwt / export_sa in engine.hip)
+test_builder            -> sa_build.hip (+ k_pack_blocks, export_bwt / export_sa in engine_index.hip)
 test_occ4_every_row     -> occ.h on both layouts' producers: k_pack_blocks (built), k_relayout (loaded)
 test_derived_sa_and_coordinates -> sa2pos.hip: k_sa_link / k_sa_jump / k_sa_sample, k_expand_sa,
                            k_sa2pos_full / k_sa2pos_walk

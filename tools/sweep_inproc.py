@@ -21,7 +21,7 @@ import bench  # noqa: E402
 from ibwa_amd import engine as E  # noqa: E402
 
 
-# engine defaults of the options a config may set (engine.hip)
+# engine defaults of the options a config may set (engine_ctx.h)
 DEFAULTS = {"gap_early_iters": 3000, "gap_early_entries": 1000, "gap_iter_budget": 8000,
             "gap_resume": 1, "gap_resume_gb": 48,
             "coop_roots": 1, "gap_reads_per_chunk": 16 << 20,
