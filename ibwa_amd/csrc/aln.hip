@@ -147,19 +147,27 @@ __device__ __forceinline__ uint32_t strand_base(uint32_t c, int a, bool comp) {
 // The compact record's byte stream (engine.h AlnArgs::cw) as width_pair produces it: byte `off` of
 // the stream goes to bits 8 * (off & 3) of word off >> 2; the accumulator carries a partial word from
 // the full-length chains into the seed chains.
+// STAGE: the record is staged in LDS (k_width<true>), word w of the block's lane t at
+// wrec[w * (blockDim.x + 1) + t] -- `words` then points at the lane's word 0 there and `stride` is
+// blockDim.x + 1; else `words` is the record in memory and stride is 1.
+template <bool STAGE>
 struct RecOut {
-  uint32_t *words;  // the record's width bytes (word 1 + cw_rw of the record)
+  using Ptr = typename std::conditional<STAGE, __attribute__((address_space(3))) uint32_t *, uint32_t *>::type;
+  Ptr words;        // the record's word 0
+  uint32_t stride;  // words between the record's consecutive words
+  uint32_t wb;      // first word of the width bytes (1 + cw_rw)
   uint32_t off, acc;
+  __device__ __forceinline__ void word(uint32_t w, uint32_t v) { words[STAGE ? w * stride : w] = v; }
   __device__ __forceinline__ void put(uint32_t byte) {
     acc |= byte << (8 * (off & 3));
     if ((off & 3) == 3) {
-      words[off >> 2] = acc;
+      word(wb + (off >> 2), acc);
       acc = 0;
     }
     ++off;
   }
   __device__ __forceinline__ void flush() {
-    if (off & 3) words[off >> 2] = acc;
+    if (off & 3) word(wb + (off >> 2), acc);
     acc = 0;
   }
 };
@@ -177,7 +185,12 @@ __device__ __forceinline__ uint32_t rec_byte(uint2 a, uint2 b, uint32_t pa, uint
 // stays on one row (suffix at q-1) exactly when q > 0 and text[q-1] == c; otherwise the interval
 // is empty and the reference resets it.  Mode 0: Occ steps; 1: the interval became one row at
 // the last step -- this step is an Occ step that also loads SA[k]; 2: text steps (suffix at t)
-// from a window of two 2-bit text words (32 symbols).  Every mode issues its loads in the same
+// from a window of two 2-bit text words (32 symbols); 3: table steps after a reset (rdep > 0) -- the
+// interval after the d symbols since the reset is the level-table entry of their string (as the
+// chain's leading steps in width_pair), one 8 B load instead of two Occ blocks at the depths where
+// k - 1 and l lie far apart; t holds the string's code (newest symbol least significant) and wi the
+// depth d, both dead outside text mode.  An N or an empty entry resets again (d = 0), one row goes to
+// mode 1 as after an Occ step, and at depth rdep the chain goes on with Occ steps.  Every mode issues its loads in the same
 // round trip as the other chain's and the other lanes' (the chains stay in lockstep), and the text
 // windows are refilled at the 16-position blocks' first step (`refresh`), for the block's 16 steps at
 // once: text-mode lanes then load in the same steps, so the wave waits once per block for them
@@ -199,9 +212,12 @@ __device__ __forceinline__ bool win_has(const WChain &h, uint32_t p) {
 }
 
 // the step's loads (issued for both chains before either is consumed: one round trip)
+// index of level e's first entry (ltab_off for 1 <= e <= 15, in 32 bits)
+__device__ __forceinline__ uint32_t ltab_off32(uint32_t e) { return (0x55555555u >> (32u - 2u * e)) + 3u; }
+
 __device__ __forceinline__ void wchain_load(const IndexView &ix, const uint32_t *sa, const uint32_t *tx,
-                                            const WChain &h, uint32_t c, WLoad &x, bool refresh) {
-  fetch1(ix, h.k - 1, h.l, c & 3, c < 4 && h.mode != 2, x.f);
+                                            const uint2 *lt, const WChain &h, uint32_t c, WLoad &x, bool refresh) {
+  fetch1(ix, h.k - 1, h.l, c & 3, c < 4 && h.mode < 2, x.f);
   x.q = 0;
   if (h.mode == 1) x.q = sa[h.k];
   // the next 16 steps read text positions p, p - 1, ..., p - 15 (p = t - 1): a window from word
@@ -215,9 +231,35 @@ __device__ __forceinline__ void wchain_load(const IndexView &ix, const uint32_t 
     x.w = tx[x.wi];
     x.w2 = tx[x.wi + 1];
   }
+  if (h.mode == 3) {
+    // the entry of the string since the reset followed by c, as {w, w2}; an N reads as empty
+    x.w = 1u;
+    x.w2 = 0u;
+    if (c < 4) {
+      const uint2 e = lt[ltab_off32(h.wi + 1u) + (h.t << 2 | c)];
+      x.w = e.x;
+      x.w2 = e.y;
+    }
+  }
 }
 
-__device__ __forceinline__ void wchain_step(const IndexView &ix, bool jump, WChain &h, uint32_t c, const WLoad &x) {
+// rdep: table steps after a reset down to this depth (0: none); nt counts the steps taken in mode 3
+__device__ __forceinline__ void wchain_step(const IndexView &ix, bool jump, uint32_t rdep, WChain &h, uint32_t c,
+                                            const WLoad &x, uint32_t &nt) {
+  if (h.mode == 3) {
+    ++nt;
+    if (x.w > x.w2) {  // N or no such string: reset, the symbol is not applied again
+      h.k = 0; h.l = ix.seq_len; ++h.bid; h.t = 0; h.wi = 0;
+      return;
+    }
+    h.k = x.w;
+    h.l = x.w2;
+    h.t = h.t << 2 | c;
+    ++h.wi;
+    if (jump && h.k == h.l) h.mode = 1;
+    else if (h.wi == rdep) h.mode = 0;
+    return;
+  }
   if (h.mode == 2) {
     if (x.tl) { h.w = x.w; h.w2 = x.w2; h.wi = x.wi; }
     const uint32_t p = h.t - 1u;
@@ -225,7 +267,8 @@ __device__ __forceinline__ void wchain_step(const IndexView &ix, bool jump, WCha
     if (h.t > 0 && c < 4 && ((tw >> (2 * (p & 15))) & 3u) == c) {
       --h.t;  // still one row: k == l stays, width 1
     } else {
-      h.k = 0; h.l = ix.seq_len; ++h.bid; h.mode = 0;
+      h.k = 0; h.l = ix.seq_len; ++h.bid; h.mode = rdep ? 3u : 0u;
+      h.t = 0; h.wi = 0;  // mode 3's string and depth (mode 0 reads neither)
     }
     return;
   }
@@ -246,6 +289,7 @@ __device__ __forceinline__ void wchain_step(const IndexView &ix, bool jump, WCha
   } else if (jump && !reset && h.k == h.l) {
     h.mode = 1;
   }
+  if (reset && rdep) { h.mode = 3; h.t = 0; h.wi = 0; }
 }
 
 // two bwt_cal_width chains in lockstep (bwtaln.c:54-78): str on ixa -> wa, strand-1 str on
@@ -254,12 +298,16 @@ __device__ __forceinline__ void wchain_step(const IndexView &ix, bool jump, WCha
 // so the L2 merges them into whole lines instead of 16 partial writes far apart).
 // With sa0/sa1 and tx0/tx1 (the exact path's full SA and 2-bit text per strand) one-row
 // intervals step from the text (wchain_step).
-__device__ __forceinline__ void width_pair(const IndexView ixa, const IndexView ixb, int L, const uint8_t *s, bool comp,
-                                           uint2 *wa, uint2 *wb, uint32_t *lw = nullptr, RecOut *rec = nullptr,
-                                           uint32_t clamp = 0, int nb = 4, uint32_t *rd = nullptr,
-                                           const uint32_t *sa0 = nullptr, const uint32_t *sa1 = nullptr,
-                                           const uint32_t *tx0 = nullptr, const uint32_t *tx1 = nullptr,
-                                           const uint2 *lta = nullptr, const uint2 *ltb = nullptr, int tdep = 0) {
+// rec / rd: the compact record's width bytes, and whether the read's words (record words 1 ...) go out too.
+template <bool STAGE = false>
+__device__ __forceinline__ uint32_t width_pair(const IndexView ixa, const IndexView ixb, int L, const uint8_t *s, bool comp,
+                                               uint2 *wa, uint2 *wb, uint32_t *lw = nullptr,
+                                               RecOut<STAGE> *rec = nullptr, uint32_t clamp = 0, int nb = 4,
+                                               bool rd = false, const uint32_t *sa0 = nullptr,
+                                               const uint32_t *sa1 = nullptr, const uint32_t *tx0 = nullptr,
+                                               const uint32_t *tx1 = nullptr, const uint2 *lta = nullptr,
+                                               const uint2 *ltb = nullptr, int tdep = 0, uint32_t rdep = 0) {
+  uint32_t nt = 0;  // steps taken from a table after a reset
   WChain A{0u, ixa.seq_len, 0u, 0u, 0u, 0xFFFFFFFFu, 0u, 0u};
   WChain B{0u, ixb.seq_len, 0u, 0u, 0u, 0xFFFFFFFFu, 0u, 0u};
   uint32_t lwa = 0, lwb = 0;  // sum of log2(width) over the positions (diagnostics)
@@ -311,21 +359,21 @@ __device__ __forceinline__ void width_pair(const IndexView ixa, const IndexView 
         uint32_t cb = strand_base(ca, 1, comp);
         const bool tA = FIRST && t < TMAX && t < da, tB = FIRST && t < TMAX && t < db;
         WLoad xa, xb;
-        if (!tA) wchain_load(ixa, sa0, tx0, A, ca, xa, t == 0);
-        if (!tB) wchain_load(ixb, sa1, tx1, B, cb, xb, t == 0);
+        if (!tA) wchain_load(ixa, sa0, tx0, lta, A, ca, xa, t == 0);
+        if (!tB) wchain_load(ixb, sa1, tx1, ltb, B, cb, xb, t == 0);
         if (FIRST && t < TMAX && tA) {
           A.k = ta[t < TMAX ? t : 0].x;
           A.l = ta[t < TMAX ? t : 0].y;
           if (t == da - 1 && sa0 != nullptr && A.k == A.l) A.mode = 1;  // as an Occ step to one row would
         } else {
-          wchain_step(ixa, sa0 != nullptr, A, ca, xa);
+          wchain_step(ixa, sa0 != nullptr, rdep, A, ca, xa, nt);
         }
         if (FIRST && t < TMAX && tB) {
           B.k = tb[t < TMAX ? t : 0].x;
           B.l = tb[t < TMAX ? t : 0].y;
           if (t == db - 1 && sa1 != nullptr && B.k == B.l) B.mode = 1;
         } else {
-          wchain_step(ixb, sa1 != nullptr, B, cb, xb);
+          wchain_step(ixb, sa1 != nullptr, rdep, B, cb, xb, nt);
         }
         ba[t] = make_uint2(A.l - A.k + 1, A.bid);
         lwa += 31 - __builtin_clz(A.l - A.k + 1);
@@ -349,7 +397,7 @@ __device__ __forceinline__ void width_pair(const IndexView ixa, const IndexView 
           pb = bb[t].x;
           x |= ((uint32_t)s[base + t] & 3u) << (2 * t);
         }
-      if (rd) rd[base >> 4] = x;
+      if (rd) rec->word(1u + ((uint32_t)base >> 4), x);
     }
   };
   if (L > 0) block(0, std::true_type{});
@@ -363,17 +411,25 @@ __device__ __forceinline__ void width_pair(const IndexView ixa, const IndexView 
     lw[2] = A.bid;
     lw[3] = B.bid;
   }
+  return nt;
 }
 
-__global__ void __launch_bounds__(256) k_width(AlnArgs A) {
-  const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane >= A.n) return;
+// The staged records of a block (k_width<true>): cw_words words per lane, word-interleaved by lane with
+// one word of padding per row (RecOut), so that the lanes' own stores and the copy-out's loads both
+// fall in distinct banks.
+extern __shared__ uint32_t wrec[];
+
+// One read's chains.  Returns the steps they took from a table after a reset.  STAGE: only the
+// compact-record launch (A.cw, no A.feat), its record into wrec instead of memory.
+template <bool STAGE>
+__device__ __forceinline__ uint32_t width_lane(const AlnArgs &A, int64_t lane) {
   const int64_t r = A.ids ? A.ids[lane] : lane;
   const int L = (int)A.len[r];
   const uint8_t *s = A.seq + A.off[r];
   const bool comp = A.o.mode & MODE_COMPREAD;
   const uint32_t *sa0 = A.jsa[0], *sa1 = A.jsa[1], *tx0 = A.jtxt[0], *tx1 = A.jtxt[1];
   const int tdep = A.ltab[0] ? (int)min(A.tab_k + 1u, 15u) : 0;  // leading steps from the level tables
+  const uint32_t rdep = A.tab_reset ? (uint32_t)tdep : 0u;       // ... and the steps after a reset
   uint2 *w0 = A.wbuf + (uint64_t)lane * A.wstride;
   uint2 *w1 = w0 + A.wlen1;
   uint2 *sw0 = w1 + A.wlen1;
@@ -383,39 +439,82 @@ __global__ void __launch_bounds__(256) k_width(AlnArgs A) {
     for (int j = 0; j < L; ++j) nN += s[j] > 3;
     A.nN[lane] = (uint16_t)(nN > 0xFFFFu ? 0xFFFFu : nN);
   }
-  if (A.feat) {
+  if (!STAGE && A.feat) {
     // search-cost features: sum of log2(width) over both full-length chains, and the seed's
     uint32_t f[4] = {0, 0, 0, 0}, g[4] = {0, 0, 0, 0};
-    width_pair(A.ix[0], A.ix[1], L, s, comp, w0, w1, f);
-    if (L > A.o.seed_len) width_pair(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, g);
+    width_pair<false>(A.ix[0], A.ix[1], L, s, comp, w0, w1, f);
+    if (L > A.o.seed_len) width_pair<false>(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, g);
     A.feat[lane * 4 + 0] = (uint16_t)(f[0] + f[1]);
     A.feat[lane * 4 + 1] = (uint16_t)(g[0] + g[1]);
     A.feat[lane * 4 + 2] = (uint16_t)(f[2] < f[3] ? f[2] : f[3]);
     A.feat[lane * 4 + 3] = (uint16_t)(g[2] < g[3] ? g[2] : g[3]);
-    return;
+    return 0;
   }
-  if (A.cw) {
+  if (STAGE || A.cw) {
     // the compact record (engine.h AlnArgs::cw), built from the chains' registers
-    uint32_t *rec = A.cw + (uint64_t)lane * A.cw_words;
+    RecOut<STAGE> ro;
+    if constexpr (STAGE) {
+      ro.words = (__attribute__((address_space(3))) uint32_t *)wrec + threadIdx.x;
+      ro.stride = blockDim.x + 1u;
+      // the words this read does not write (read words past its length, the seed's bytes of a read no
+      // longer than the seed) leave as zeros
+      for (uint32_t w = 0; w < A.cw_words; ++w) ro.word(w, 0u);
+    } else {
+      ro.words = A.cw + (uint64_t)lane * A.cw_words;
+      ro.stride = 1u;
+    }
+    ro.wb = 1u + A.cw_rw;
+    ro.off = ro.acc = 0u;
     uint32_t nN = 0;
     for (int j = 0; j < L; ++j) nN += s[j] > 3;
     const int md = A.o.fnr_pos ? (int)A.maxdiff_tab[L] : A.o.max_diff;
-    rec[0] = (uint32_t)L | (nN < 255u ? nN : 255u) << 16 | (uint32_t)md << 24;
-    RecOut ro{rec + 1 + A.cw_rw, 0u, 0u};
-    width_pair(A.ix[0], A.ix[1], L, s, comp, w0, w1, nullptr, &ro, (uint32_t)md + 1u, 4, rec + 1, sa0, sa1, tx0, tx1,
-               A.ltab[0], A.ltab[1], tdep);
+    ro.word(0u, (uint32_t)L | (nN < 255u ? nN : 255u) << 16 | (uint32_t)md << 24);
+    uint32_t nt = width_pair<STAGE>(A.ix[0], A.ix[1], L, s, comp, w0, w1, nullptr, &ro, (uint32_t)md + 1u, 4, true, sa0,
+                                    sa1, tx0, tx1, A.ltab[0], A.ltab[1], tdep, rdep);
     while (ro.off < A.wlen1) ro.put(0u);  // positions past this read's length
     if (L > A.o.seed_len)
-      width_pair(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, nullptr, &ro,
-                 (uint32_t)A.o.max_seed_diff + 1u, 3, nullptr, sa0, sa1, tx0, tx1, A.ltab[0], A.ltab[1], tdep);
+      nt += width_pair<STAGE>(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, nullptr, &ro,
+                              (uint32_t)A.o.max_seed_diff + 1u, 3, false, sa0, sa1, tx0, tx1, A.ltab[0], A.ltab[1],
+                              tdep, rdep);
     ro.flush();
-    return;
+    return nt;
   }
-  width_pair(A.ix[0], A.ix[1], L, s, comp, w0, w1, nullptr, nullptr, 0, 4, nullptr, sa0, sa1, tx0, tx1, A.ltab[0],
-             A.ltab[1], tdep);
+  uint32_t nt = width_pair<false>(A.ix[0], A.ix[1], L, s, comp, w0, w1, nullptr, nullptr, 0, 4, false, sa0, sa1, tx0, tx1,
+                           A.ltab[0], A.ltab[1], tdep, rdep);
   if (L > A.o.seed_len)
-    width_pair(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, nullptr, nullptr, 0, 4,
-               nullptr, sa0, sa1, tx0, tx1, A.ltab[0], A.ltab[1], tdep);
+    nt += width_pair<false>(A.ix[0], A.ix[1], A.o.seed_len, s + (L - A.o.seed_len), comp, sw0, sw1, nullptr, nullptr, 0, 4,
+                     false, sa0, sa1, tx0, tx1, A.ltab[0], A.ltab[1], tdep, rdep);
+  return nt;
+}
+
+template <bool STAGE>
+__global__ void __launch_bounds__(256) k_width(AlnArgs A) {
+  const int64_t lane0 = (int64_t)blockIdx.x * blockDim.x;  // the block's first lane
+  const int64_t lane = lane0 + threadIdx.x;
+  // a lane past the batch runs no chains, but takes part in the barrier and the reduction below
+  uint32_t nt = lane < A.n ? width_lane<STAGE>(A, lane) : 0u;
+  if constexpr (STAGE) {
+    // The block's records are one contiguous range of A.cw: consecutive threads store consecutive
+    // words of it, whole lines at a time, instead of each lane its own words one by one along its walk.
+    __syncthreads();
+    const uint32_t cw = A.cw_words, bd = blockDim.x;
+    const int64_t left = A.n - lane0;
+    const uint32_t total = (uint32_t)(left < (int64_t)bd ? left : (int64_t)bd) * cw;
+    uint32_t *dst = A.cw + (uint64_t)lane0 * cw;
+    const uint32_t dq = bd / cw, dr = bd % cw;
+    uint32_t q = threadIdx.x / cw, w = threadIdx.x % cw;  // word i = q * cw + w: word w of the block's lane q
+    for (uint32_t i = threadIdx.x; i < total; i += bd) {
+      dst[i] = wrec[w * (bd + 1u) + q];
+      q += dq;
+      w += dr;
+      if (w >= cw) { w -= cw; ++q; }
+    }
+  }
+  if (A.tab_steps) {
+    // one atomic per wave
+    for (int o = 32; o > 0; o >>= 1) nt += __shfl_xor(nt, o);
+    if ((threadIdx.x & 63u) == 0 && nt) atomicAdd(A.tab_steps, (unsigned long long)nt);
+  }
 }
 
 // bwt_match_exact_alt (bwt.c:235-250) over str[0..i-1] from (k, l)
@@ -664,7 +763,14 @@ __global__ void __launch_bounds__(256) k_occ4(IndexView ix, int64_t n, const uin
 hipError_t launch_width(const AlnArgs &a, int block, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
   uint64_t grid = (a.n + block - 1) / block;
-  hipLaunchKernelGGL(k_width, dim3((unsigned)grid), dim3(block), 0, st, a);
+  // The records staged in LDS when that costs no residency: the kernel's registers allow 3 waves per
+  // SIMD, 12 per CU, and that many waves' blocks must fit the CU's 160 KiB of LDS.
+  const size_t lds = (size_t)a.cw_words * ((size_t)block + 1) * 4;
+  const size_t per_cu = (12 * 64 + (size_t)block - 1) / (size_t)block;
+  if (a.cw_stage && a.cw && !a.feat && block % 64 == 0 && lds <= (64u << 10) && lds * per_cu <= (160u << 10))
+    hipLaunchKernelGGL(k_width<true>, dim3((unsigned)grid), dim3(block), lds, st, a);
+  else
+    hipLaunchKernelGGL(k_width<false>, dim3((unsigned)grid), dim3(block), 0, st, a);
   return hipGetLastError();
 }
 

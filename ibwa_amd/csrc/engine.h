@@ -19,6 +19,7 @@ enum CounterSlot {
   CTR_WIDE_STREAM = 2,  // fill of a wide retry launch's own hit stream
   CTR_HANDED_ON = 3,    // count of select_handed_on
   CTR_RESUMED = 5,      // count of select_resumed
+  CTR_WIDTH_TAB = 6,    // AlnArgs::tab_steps
   CTR_TAIL_JUMPS = 7,   // GapArgs::tail_jumps
 };
 // The cooperative launches' bump pointers share another (ibwa_ctx::coop.c_next): a u32 and, past it, a u64.
@@ -77,6 +78,13 @@ struct AlnArgs {
   // 15) steps from them; nullptr: off
   const uint2 *ltab[2];
   uint32_t tab_k;
+  // non-zero: a chain also takes the steps after a reset (empty interval or N) from the tables, one
+  // 8 B load per step down to the same depth; tab_steps (may be null): the launch adds those steps
+  uint32_t tab_reset;
+  unsigned long long *tab_steps;
+  // non-zero: the compact records are staged in LDS and leave as whole lines at the block's end
+  // (launch_width falls back to the lanes' own word stores when the staging would cost residency)
+  uint32_t cw_stage;
   AlnOpt o;
 };
 

@@ -174,6 +174,7 @@ int run_setup(Run &R, int batch_max_len) {
   c->stats.resume_records_peak = c->stats.resume_records_cap = 0;
   c->stats.coop_pages_peak = c->stats.coop_pages_cap = 0;
   c->stats.n_tail_jumps = 0;
+  c->stats.n_width_tab_steps = 0;
   A.cap = c->stack_cap;
   return 0;
 }
@@ -537,7 +538,9 @@ int first_pass_persistent(Run &R) {
     A.ltab[0] = c->index.ltab[0].as<uint2>();
     A.ltab[1] = c->index.ltab[1].as<uint2>();
     A.tab_k = (uint32_t)c->index.ltab_K;
+    A.tab_reset = c->width_tab == 2;
   }
+  A.cw_stage = (uint32_t)c->width_rec_stage;
   const FirstPassPlan P = plan_first_pass(R);
   const bool lw = P.lw, resume = P.resume;
   const int64_t chunk = P.chunk;
@@ -566,6 +569,11 @@ int first_pass_persistent(Run &R) {
   if (int rc = c->d_counter.ensure(64)) return rc;
   HIPCHK(zero_async(counter(c, CTR_STREAM), 8, c->stream));
   HIPCHK(zero_async(counter(c, CTR_TAIL_JUMPS), 8, c->stream));  // GapArgs::tail_jumps
+  HIPCHK(zero_async(counter(c, CTR_WIDTH_TAB), 8, c->stream));   // AlnArgs::tab_steps (every k_width of the run)
+  A.tab_steps = counter(c, CTR_WIDTH_TAB);
+  c->res.diag_w.clear();
+  c->res.diag_cw.clear();
+  c->res.diag_shape[0] = c->res.diag_shape[1] = c->res.diag_shape[2] = 0;
   for (int64_t b0 = 0; b0 < n; b0 += chunk) {
     const int64_t cnt = std::min(chunk, n - b0);
     AlnArgs B = A;
@@ -631,9 +639,26 @@ int first_pass_persistent(Run &R) {
       HIPCHK(hipMemsetAsync(c->d_prof.p, 0, 256, c->stream));
       G.prof = c->d_prof.as<unsigned long long>();
     }
+    const bool keep_w = c->diag_width && b0 == 0;  // ibwa_batch_diag 3 / 4: the first chunk's k_width outputs
+    if (keep_w) {
+      // zeros where k_width writes nothing (past a read's length), so the copies compare byte for byte
+      HIPCHK(hipMemsetAsync(B.wbuf, 0, (uint64_t)cnt * A.wstride * 8, c->stream));
+      if (lw) HIPCHK(hipMemsetAsync(B.cw, 0, (uint64_t)cnt * P.cw_words * 4, c->stream));
+    }
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
     HIPCHK(launch_width(B, c->block, c->stream));
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    if (keep_w) {
+      // before k_gapped: its gap_shadow rewrites the rows, and the later passes reuse the buffer
+      c->res.diag_w.resize((uint64_t)cnt * A.wstride);
+      c->res.diag_cw.resize(lw ? (uint64_t)cnt * P.cw_words : 0);
+      c->res.diag_shape[0] = (uint64_t)cnt;
+      c->res.diag_shape[1] = A.wstride;
+      c->res.diag_shape[2] = lw ? P.cw_words : 0;
+      HIPCHK(hipStreamSynchronize(c->stream));
+      HIPCHK(hipMemcpy(c->res.diag_w.data(), B.wbuf, c->res.diag_w.size() * 8, hipMemcpyDeviceToHost));
+      if (lw) HIPCHK(hipMemcpy(c->res.diag_cw.data(), B.cw, c->res.diag_cw.size() * 4, hipMemcpyDeviceToHost));
+    }
     HIPCHK(launch_gapped(G, counter(c, CTR_CLAIM), P.blocks, P.block, false, c->stream));
     HIPCHK(hipEventRecord(c->ev[2], c->stream));
     HIPCHK(hipEventSynchronize(c->ev[2]));
@@ -1150,6 +1175,10 @@ int finish_run(Run &R) {
     unsigned long long tj = 0;
     HIPCHK(hipMemcpy(&tj, counter(c, CTR_TAIL_JUMPS), 8, hipMemcpyDeviceToHost));
     c->stats.n_tail_jumps = (int64_t)tj;
+    if (R.A.tab_steps) {
+      HIPCHK(hipMemcpy(&tj, counter(c, CTR_WIDTH_TAB), 8, hipMemcpyDeviceToHost));
+      c->stats.n_width_tab_steps = (int64_t)tj;
+    }
   }
   c->stats.ms_retry = R.ms_r + R.res_ms;
   c->stats.n_retry = (int64_t)c->res.retry_ids.size() + R.res_ok;
@@ -1187,6 +1216,17 @@ int ibwa_batch_retry_info(const ibwa_ctx_t *c, int64_t *ids, uint8_t *pass, int6
 }
 
 int ibwa_batch_diag(const ibwa_ctx_t *c, int what, void *out, uint64_t cap_bytes) {
+  if (what >= 3 && what <= 5) {
+    // the first-pass chunk's k_width outputs, kept by the run under option diag_width (the whole batch
+    // when it ran as one chunk): 3 its width rows, 4 its compact records, 5 their shape {reads, wstride,
+    // cw_words}
+    const void *src = what == 3 ? (const void *)c->res.diag_w.data()
+                      : what == 4 ? (const void *)c->res.diag_cw.data() : (const void *)c->res.diag_shape;
+    const uint64_t need3 = what == 3 ? c->res.diag_w.size() * 8 : what == 4 ? c->res.diag_cw.size() * 4 : 24;
+    if (cap_bytes < need3) return fail(IBWA_EINVAL, "diag buffer too small");
+    if (need3) memcpy(out, src, need3);
+    return 0;
+  }
   if (what == 2) {
     const uint64_t need2 = (uint64_t)c->batch.n * 4;
     if (cap_bytes < need2) return fail(IBWA_EINVAL, "diag buffer too small");

@@ -312,7 +312,9 @@ int ibwa_ctx_set_option(ibwa_ctx_t *c, const char *key, long value) {
   else if (k == "exact_jump") c->exact_jump = value != 0;
   else if (k == "jump_derive") c->jump_derive = value != 0;
   else if (k == "width_jump" && value >= 0 && value <= 2) c->width_jump = (int)value;
-  else if (k == "width_tab" && (value == 0 || value == 1)) c->width_tab = (int)value;
+  else if (k == "width_tab" && value >= 0 && value <= 2) c->width_tab = (int)value;
+  else if (k == "width_rec_stage" && (value == 0 || value == 1)) c->width_rec_stage = (int)value;
+  else if (k == "diag_width") c->diag_width = value != 0;
   else if (k == "gap_tail_tab" && (value == 0 || value == 1)) c->gap_tail_tab = (int)value;
   else if (k == "diag") c->diag = value != 0;
   else if (k == "sa_walk") c->sa_walk = value != 0;

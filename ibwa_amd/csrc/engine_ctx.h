@@ -186,6 +186,11 @@ struct Results {
   unsigned long long stream_total = 0;  // hit-stream slots of the last first-pass launch
   bool naln_on_host = true;  // h_naln mirrors d_naln
   bool fetched = false;       // the batch's results are on the host (fetch_to_host; a run resets it)
+  // option diag_width: the first-pass chunk's width rows and compact records as k_width wrote them
+  // (ibwa_batch_diag 3 / 4), and their shape {reads, wstride, cw_words}
+  std::vector<uint2> diag_w;
+  std::vector<uint32_t> diag_cw;
+  uint64_t diag_shape[3] = {0, 0, 0};
 };
 
 // Scratch and device outputs of the first pass, the wide pass and the general kernels.
@@ -272,7 +277,9 @@ struct ibwa_ctx : ibwa::CtxQueue {
   int coop_roots = 1;                               // option: level 0 of the heavy reads by k_coop_roots
   int jump_derive = 1;        // option: derive the jump arrays for a loaded index when HBM allows
   int exact_jump = 1;
-  int width_tab = 1;           // option: k_width's first steps from the level tables (first pass)
+  int width_tab = 2;           // option: k_width's steps from the level tables (1: a chain's first; 2: and after resets)
+  int width_rec_stage = 1;     // option: k_width stages its compact records in LDS and stores them whole
+  int diag_width = 0;          // option: keep the first-pass chunk's k_width outputs (ibwa_batch_diag 3 / 4)
   int gap_tail_tab = 1;        // option: exact tails of nodes stored by their strings jump by the level tables
   int width_jump = 1;         // option: k_width steps one-row intervals from the text (2: derive SA / text for it)
   int sa_walk = 0;                     // option: always walk the sampled SA (parity / low-memory)

@@ -35,7 +35,7 @@ class RunStats(c.Structure):
                 ("n_resumed", c.c_int64), ("resume_records", c.c_int64),
                 ("resume_records_peak", c.c_int64), ("resume_records_cap", c.c_int64),
                 ("coop_pages_peak", c.c_int64), ("coop_pages_cap", c.c_int64), ("ms_alloc", c.c_double),
-                ("n_tail_jumps", c.c_int64)]
+                ("n_tail_jumps", c.c_int64), ("n_width_tab_steps", c.c_int64)]
 
 
 class RefSeq(c.Structure):
@@ -312,6 +312,27 @@ class Engine:
         hp = np.zeros(self.n, np.uint32)
         _chk(lib().ibwa_batch_diag(self.h, 2, hp.ctypes.data, hp.nbytes))
         return hp
+
+    def _width_shape(self):
+        sh = np.zeros(3, np.uint64)
+        _chk(lib().ibwa_batch_diag(self.h, 5, sh.ctypes.data, sh.nbytes))
+        return int(sh[0]), int(sh[1]), int(sh[2])
+
+    def width_rows(self):
+        """The first-pass chunk's width rows as k_width wrote them, uint32[reads, wstride, 2] of {width, bid}
+        (option diag_width=1, a batch of one chunk), ibwa_batch_diag 3."""
+        n, ws, _ = self._width_shape()
+        w = np.zeros((n, ws, 2), np.uint32)
+        _chk(lib().ibwa_batch_diag(self.h, 3, w.ctypes.data, w.nbytes))
+        return w
+
+    def width_records(self):
+        """Its compact records, uint32[reads, cw_words]; no rows when the first pass ran without them
+        (option diag_width=1), ibwa_batch_diag 4."""
+        n, _, cw = self._width_shape()
+        r = np.zeros((n if cw else 0, cw), np.uint32)
+        _chk(lib().ibwa_batch_diag(self.h, 4, r.ctypes.data, r.nbytes))
+        return r
 
     @staticmethod
     def device_bytes():

@@ -218,6 +218,9 @@ typedef struct {
 	double ms_alloc;             /* wall time the run spent allocating device buffers (hipMalloc) */
 	int64_t n_tail_jumps;        /* exact tails the first pass started from a level-table entry
 	                                ("gap_tail_tab"; 0 when the option or the tables are off) */
+	int64_t n_width_tab_steps;   /* steps k_width's chains took from a level-table entry after a reset
+	                                ("width_tab" 2; 0 when the option or the tables are off), summed over
+	                                the run's k_width launches */
 } ibwa_run_stats_t;
 int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
 
@@ -230,8 +233,14 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *   "width_jump" (0/1/2, default 1) k_width steps one-row intervals from the 2-bit text
  *                                  (1: when those arrays are resident; 2: derive them for a
  *                                  gapped batch too; 0: Occ steps only) -- same widths
- *   "width_tab" (0/1, default 1)   k_width takes a chain's first steps (up to gap_tab_k + 1) from
- *                                  the level tables, one round trip for all -- same widths
+ *   "width_tab" (0/1/2, default 2) k_width takes a chain's first steps (up to gap_tab_k + 1) from
+ *                                  the level tables, one round trip for all; 2: also the steps after
+ *                                  every reset (empty interval or N), one 8 B entry per step instead of
+ *                                  two Occ blocks, down to the same depth -- same widths
+ *   "width_rec_stage" (0/1, default 1) k_width builds a block's compact first-pass records in LDS and
+ *                                  stores them as whole lines at the block's end (0, or when the
+ *                                  staging would cost residency: each lane stores its own words
+ *                                  along its walk) -- same records
  *   "gap_tail_tab" (0/1, default 1) first pass: the exact tail (bwt_match_exact_alt) of a node stored
  *                                  by its string takes its steps down to depth gap_tab_k + 1 from one
  *                                  level-table entry, one round trip for all (0: one Occ step per
@@ -278,7 +287,8 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *                                  resident
  *   Test and diagnostics hooks: "gap_stream_per_read" (4), "gap_stream_min" (1 << 20) the first
  *   pass's hit-stream size; "gap_resume_records", "coop_pool_pages" buffer sizes in records / pages;
- *   "diag" (0) per-read iterations and k_width features; "sw_stop" (0) stop k_sw after a pass. */
+ *   "diag" (0) per-read iterations and k_width features; "diag_width" (0) keep the first-pass
+ *   chunk's k_width outputs for ibwa_batch_diag 3 / 4; "sw_stop" (0) stop k_sw after a pass. */
 int ibwa_ctx_set_option(ibwa_ctx_t *ctx, const char *key, long value);
 
 /* The sources this library was built from: the first 16 hex digits of the SHA-256 of the
@@ -316,7 +326,13 @@ int ibwa_batch_retry_info(const ibwa_ctx_t *ctx, int64_t *ids, uint8_t *pass, in
  * sum of log2 width over both full-length chains, the same over the seed chains, the smaller
  * restart count of the two full chains, of the two seed chains).  what 2 (no option needed): per
  * read the pops (bwtgap.c:129) the first pass made before leaving its resume state, 0 if it left
- * none (uint32[n]): the point where the read's search moves from k_gapped to k_coop. */
+ * none (uint32[n]): the point where the read's search moves from k_gapped to k_coop.
+ * With option "diag_width" = 1 (persistent gapped path), valid for a batch that ran as one chunk:
+ * what 3 = the width rows of the first-pass chunk as k_width wrote them, before the search updates
+ * them (uint2[n][wstride]: {width, bid} per position of the two full-length chains, wlen1 entries
+ * each, then of the two seed chains; zeros where k_width writes nothing); 4 = its compact records
+ * (uint32[n][cw_words]; empty when the first pass did not run with its widths in LDS); 5 = their
+ * shape (uint64[3]: reads, wstride, cw_words). */
 int ibwa_batch_diag(const ibwa_ctx_t *ctx, int what, void *out, uint64_t cap_bytes);
 
 /* Tuning knobs (0 = default): per-lane stack entries, per-read hit slots, block size */

@@ -28,7 +28,8 @@ DEFAULTS = {"gap_early_iters": 3000, "gap_early_entries": 1000, "gap_iter_budget
             "gap_resume_iters": 2000, "gap_resume_entries": 300, "gap_tail_lanes": 16, "gap_tail_iters": 200,
             "gap_pages_per_block": 384, "gap_cap1": 8192, "gap_resume_ppb": 48, "gap_resume_cap1": 4096,
             "coop_pool_gb": 0, "gap_lw_min_waves": 8, "coop_waves_per_cu": 12,
-            "coop_stg_room": 1, "gap_resume_recs": 192, "kmer_k": -1, "gap_tab_k": -1, "width_tab": 1,
+            "coop_stg_room": 1, "gap_resume_recs": 192, "kmer_k": -1, "gap_tab_k": -1, "width_tab": 2,
+            "width_rec_stage": 1,
             "gap_tail_tab": 1, "coop_early": 1}
 
 
@@ -83,7 +84,7 @@ def main():
                    "coop_roots": st.ms_coop_roots, "coop_width": st.ms_coop_width, "n_resumed": int(st.n_resumed),
                    "resume_records": int(st.resume_records), "resume_records_peak": int(st.resume_records_peak),
                    "coop_pages_peak": int(st.coop_pages_peak), "coop_pages_cap": int(st.coop_pages_cap),
-                   "n_tail_jumps": int(st.n_tail_jumps),
+                   "n_tail_jumps": int(st.n_tail_jumps), "n_width_tab_steps": int(st.n_width_tab_steps),
                    "lib_bytes": E.Engine.device_bytes(),
                    "hits_equal_first_config": same}
             print(json.dumps(rec), flush=True)
