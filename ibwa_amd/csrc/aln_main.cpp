@@ -319,6 +319,7 @@ int fa2pac_main(int argc, char *argv[]);
 int pac_rev_main(int argc, char *argv[]);
 int pac2cspac_main(int argc, char *argv[]);
 int index_cs_main(int argc, char *argv[]);
+int stdsw_main(int argc, char *argv[]);  // stdsw_main.cpp
 
 int main(int argc, char *argv[]) {
   // Before the HIP runtime starts: host <-> device copies of every size go through the copy engines.
@@ -333,6 +334,7 @@ int main(int argc, char *argv[]) {
   if (argc >= 2 && strcmp(argv[1], "pac_rev") == 0) return pac_rev_main(argc - 1, argv + 1);
   if (argc >= 2 && strcmp(argv[1], "pac2cspac") == 0) return pac2cspac_main(argc - 1, argv + 1);
   if (argc >= 2 && strcmp(argv[1], "index_cs") == 0) return index_cs_main(argc - 1, argv + 1);
+  if (argc >= 2 && strcmp(argv[1], "stdsw") == 0) return stdsw_main(argc - 1, argv + 1);
   if (argc < 2 || strcmp(argv[1], "aln") != 0) {
     fprintf(stderr, "Usage: ibwa-amd aln [options] <prefix> <in.fq>\n"
                     "       ibwa-amd aln [options] -f <out1.sai> -F <out2.sai> <prefix> <in1.fq> <in2.fq>\n"
@@ -341,7 +343,8 @@ int main(int argc, char *argv[]) {
                     "       ibwa-amd index [-a bwtsw|div|is] [-p prefix] <in.fasta>\n"
                     "       ibwa-amd index_cs [-a bwtsw|div|is] [-p prefix] <in.fasta>\n"
                     "       ibwa-amd fa2pac <in.fasta> [<out.prefix>] | pac_rev <in.pac> <out.pac>\n"
-                    "       ibwa-amd pac2cspac <in.nt.prefix> <out.cs.prefix>\n");
+                    "       ibwa-amd pac2cspac <in.nt.prefix> <out.cs.prefix>\n"
+                    "       ibwa-amd stdsw [-g] [-T INT] [-f] [-r] [-p] <long.fa> <short.fa>\n");
     return 1;
   }
   --argc; ++argv;

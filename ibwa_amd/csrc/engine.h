@@ -286,6 +286,31 @@ hipError_t launch_pack_cigar(const uint32_t *cig, int cap, const int32_t *n_ciga
 uint64_t sw_words_per_lane(int max_len1, int max_len2);
 uint64_t sw_tb_per_lane(int max_len1, int max_len2);
 
+// Batched alignment with run-time scoring (stdaln.hip): one launch of a chunk of pairs.
+struct StdArgs {
+  const uint8_t *seq1, *seq2;     // codes < row
+  const uint64_t *off1, *off2;
+  const uint32_t *len1, *len2;
+  int64_t n;
+  int gap_open, gap_ext, gap_end, band, row, max_score;  // band <= 0: len1 + len2 of each pair
+  const int32_t *matrix;          // row x row, device
+  int type, thres;                // 0 local / 1 global; the local core's _thres
+  int max_len1;                   // sizes the eh rows in LDS
+  int eh_lds;                     // the eh rows live in LDS
+  int keep_suba;                  // the rows' maxima are kept (suba); 0: the forward pass runs twice
+  uint32_t *scratch;              // words_per_lane u32 per lane, lane-minor per wave: eh | mid | suba
+  uint64_t words_per_lane;
+  uint32_t e_eh, e_mid, e_suba;   // first word of each part
+  uint32_t mid_w;                 // cells per (M, I, D) row
+  uint8_t *tb;                    // tb_per_lane bytes (cells) per lane, lane-minor dwords per wave
+  uint64_t tb_per_lane;
+  int32_t *score, *subo, *path_len, *n_cigar;
+  int4 *ends;
+  uint32_t *cigar;
+  int cigar_cap;
+};
+hipError_t launch_stdaln(const StdArgs &a, unsigned long long *d_counter, int waves, hipStream_t st);
+
 // The packed reference in HBM, refinement windows / fix-ups and MD/NM (refine.hip).
 // The resident sequence: the set's references back to back, base g at bits 7-6 .. 1-0 of byte g / 4,
 // in 32-bit words.  launch_pac_concat builds it from the references' own .pac bytes (src, reference

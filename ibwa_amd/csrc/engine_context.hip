@@ -326,6 +326,8 @@ int ibwa_ctx_set_option(ibwa_ctx_t *c, const char *key, long value) {
   else if (k == "coop_pool_pages" && value >= 0 && value <= (1l << 24)) c->coop_pool_pages = (uint32_t)value;
   else if (k == "gap_resume_recs" && value >= 1 && value <= 65536) c->gap_resume_recs = (uint32_t)value;
   else if (k == "sw_stop" && value >= 0 && value <= 2) c->sw_stop_after = (int)value;  // SW phase timing
+  else if (k == "stdaln_suba_rows" && value >= 0) c->stdaln_suba_rows = value;
+  else if (k == "stdaln_scratch_mb" && value >= 1 && value <= (1l << 18)) c->stdaln_scratch_mb = value;
   else return fail(IBWA_EINVAL, "unknown option %s", k.c_str());
   return 0;
 }

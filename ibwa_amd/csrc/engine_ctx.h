@@ -221,6 +221,12 @@ struct SwBufs {
   DBuf scr, tbb;                // DP scratch, traceback
   DBuf cf, cc;                  // packed CIGARs: each row's first word, the words
 };
+// ibwa_stdaln_batch's buffers (kept between calls).
+struct StdBufs {
+  DBuf s1, s2, o1, o2, l1, l2, mat;
+  DBuf sc, su, pl, nc, en, cg;  // score, subo, path_len, n_cigar, ends, a chunk's CIGAR rows
+  DBuf scr, tbb, cf, cc;        // DP scratch, traceback, packed CIGARs (first words, words)
+};
 // ibwa_refine_batch's own buffers.  ibwa_pac_extract borrows them for its begins, lengths and got
 // counts (dpos, dext, dout in that order).
 struct RefineBufs {
@@ -255,6 +261,7 @@ struct ibwa_ctx : ibwa::CtxQueue {
   DBuf h2p_in, h2p_out;      // staging of ibwa_sa2pos
   // post-alignment services
   ibwa::SwBufs sw;
+  ibwa::StdBufs sd;
   ibwa::RefineBufs rf;
   ibwa::MdBufs md;
   ibwa::CsBufs cs;
@@ -333,6 +340,10 @@ struct ibwa_ctx : ibwa::CtxQueue {
   bool verbose = getenv("IBWA_VERBOSE") != nullptr;
   bool prof_phases = getenv("IBWA_PROF_PHASES") != nullptr;  // diagnostics kernel variant
   int sw_stop_after = getenv("IBWA_SW_STOP") ? atoi(getenv("IBWA_SW_STOP")) : 0;  // diagnostics
+  int64_t stdaln_scratch_mb = 32768;  // option: device scratch of one ibwa_stdaln_batch launch, MiB
+  int64_t stdaln_suba_rows = 8192;   // option: keep suba (one entry per row of seq2) up to this many rows
+  int64_t stdaln_chunks = 0;         // launches the last ibwa_stdaln_batch took
+  double stdaln_ms = 0;              // ... and their kernel time
   int diag = 0;                      // option: keep per-read first-pass iterations and k_width features
   uint32_t gap_stream_per_read = 4;     // first-pass hit-stream slots per read
   uint64_t gap_stream_min = 1u << 20;   // ... and at least this many in total

@@ -135,6 +135,11 @@ CAPI = {
                                 _vp, _vp, c.POINTER(_u64), c.POINTER(_u64)]),
     "ibwa_sw_core_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                 c.POINTER(c.c_void_p)]),
+    "ibwa_aln_param_preset": (_i, [c.c_char_p, _vp]),
+    "ibwa_stdaln_batch": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               c.POINTER(c.c_void_p), c.POINTER(_i64)]),
+    "ibwa_stdaln_check": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_stdaln_chunks": (_i, [_vp, c.POINTER(_i64), c.POINTER(c.c_double)]),
     "ibwa_ctx_load_pac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
     "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
@@ -176,6 +181,61 @@ class IbwaError(RuntimeError):
 def _chk(rc):
     if rc != 0:
         raise IbwaError(f"ibwa error {rc}: {lib().ibwa_last_error().decode()}")
+
+
+class AlnParam(c.Structure):
+    """AlnParam (stdaln.h) == ibwa_aln_param_t"""
+    _fields_ = [("gap_open", c.c_int), ("gap_ext", c.c_int), ("gap_end", c.c_int), ("matrix", c.POINTER(c.c_int32)),
+                ("row", c.c_int), ("band_width", c.c_int)]
+
+
+def aln_param(name):
+    """The preset "blast", "aa2aa" or "bwa" (ibwa_aln_param_preset) as a dict with the keys gap_open,
+    gap_ext, gap_end, matrix (row x row int32 array), row and band_width."""
+    ap = AlnParam()
+    _chk(lib().ibwa_aln_param_preset(name.encode(), c.byref(ap)))
+    mat = np.ctypeslib.as_array(ap.matrix, shape=(ap.row, ap.row)).astype(np.int32)
+    return {"gap_open": ap.gap_open, "gap_ext": ap.gap_ext, "gap_end": ap.gap_end, "matrix": mat, "row": ap.row,
+            "band_width": ap.band_width}
+
+
+def _aln_param_struct(param):
+    """dict / (gap_open, gap_ext, gap_end, matrix, row, band_width) tuple / preset name -> (AlnParam, matrix)."""
+    if isinstance(param, str):
+        param = aln_param(param)
+    if isinstance(param, dict):
+        param = (param["gap_open"], param["gap_ext"], param["gap_end"], param["matrix"],
+                 param.get("row"), param.get("band_width", 0))
+    go, ge, gend, mat, row, band = param
+    mat = np.ascontiguousarray(mat, dtype=np.int32)
+    if row is None:
+        row = int(round(mat.size ** 0.5))
+    if mat.size != row * row:
+        raise IbwaError(f"score matrix of {mat.size} entries for row {row}")
+    ap = AlnParam(int(go), int(ge), int(gend), mat.ctypes.data_as(c.POINTER(c.c_int32)), int(row), int(band))
+    return ap, mat
+
+
+def _pair_arrays(seq1s, seq2s):
+    n = len(seq1s)
+    o1 = np.zeros(n, np.uint64)
+    o2 = np.zeros(n, np.uint64)
+    l1 = np.array([len(x) for x in seq1s], np.uint32)
+    l2 = np.array([len(x) for x in seq2s], np.uint32)
+    if n:
+        o1[1:] = np.cumsum(l1[:-1])
+        o2[1:] = np.cumsum(l2[:-1])
+    s1 = np.concatenate([np.asarray(x, np.uint8) for x in seq1s] + [np.zeros(1, np.uint8)])
+    s2 = np.concatenate([np.asarray(x, np.uint8) for x in seq2s] + [np.zeros(1, np.uint8)])
+    return n, s1, o1, l1, s2, o2, l2
+
+
+def stdaln_check(seq1s, seq2s, param, mode="local", thres=1):
+    """The checks of ibwa_stdaln_batch alone (no device): raises IbwaError on a refusal."""
+    ap, _mat = _aln_param_struct(param)
+    n, s1, o1, l1, s2, o2, l2 = _pair_arrays(seq1s, seq2s)
+    _chk(lib().ibwa_stdaln_check(c.byref(ap), {"local": 0, "global": 1}[mode], thres, n, s1.ctypes.data, o1.ctypes.data,
+                                 l1.ctypes.data, s2.ctypes.data, o2.ctypes.data, l2.ctypes.data))
 
 
 def default_opt():
@@ -453,6 +513,44 @@ class Engine:
                         "".join(f"{x >> 4}{'MIDS'[x & 0xf]}" for x in cig[q:q + ncig[p]])))
             q += ncig[p]
         return out
+
+    def stdaln(self, seq1s, seq2s, param, mode="local", thres=1):
+        """Batched aln_local_core / aln_global_core for any scoring scheme (ibwa_stdaln_batch).
+        seq1s / seq2s: code arrays (each code < row); param: a preset name, aln_param()'s dict, or a
+        (gap_open, gap_ext, gap_end, matrix, row, band_width) tuple (band_width <= 0: len1 + len2).
+        Returns per pair (score, subo, path_len, start (i, j) | None, end (i, j) | None, cigar str |
+        None); as in aln_stdaln_aux a start coordinate of 0 is given as 1."""
+        ap, _mat = _aln_param_struct(param)
+        n, s1, o1, l1, s2, o2, l2 = _pair_arrays(seq1s, seq2s)
+        score = np.zeros(n, np.int32)
+        subo = np.zeros(n, np.int32)
+        plen = np.zeros(n, np.int32)
+        ends = np.zeros((n, 4), np.int32)
+        ncig = np.zeros(n, np.int32)
+        ptr = c.c_void_p()
+        tot = c.c_int64()
+        _chk(lib().ibwa_stdaln_batch(self.h, c.byref(ap), {"local": 0, "global": 1}[mode], thres, n, s1.ctypes.data,
+                                     o1.ctypes.data, l1.ctypes.data, s2.ctypes.data, o2.ctypes.data, l2.ctypes.data,
+                                     score.ctypes.data, subo.ctypes.data, plen.ctypes.data, ends.ctypes.data,
+                                     ncig.ctypes.data, c.byref(ptr), c.byref(tot)))
+        cig = np.frombuffer(c.string_at(ptr.value, 4 * max(tot.value, 0)), dtype=np.uint32).copy()
+        lib().ibwa_free(ptr)
+        out, q = [], 0
+        for p in range(n):
+            if plen[p] > 0:
+                cs = "".join(f"{x >> 4}{'MIDS'[x & 0xf]}" for x in cig[q:q + ncig[p]])
+                out.append((int(score[p]), int(subo[p]), int(plen[p]), (int(ends[p, 0]) or 1, int(ends[p, 1]) or 1),
+                            (int(ends[p, 2]), int(ends[p, 3])), cs))
+            else:
+                out.append((int(score[p]), int(subo[p]), 0, None, None, None))
+            q += ncig[p]
+        return out
+
+    def stdaln_chunks(self):
+        """(launches, kernel ms) of the last stdaln call."""
+        k, ms = c.c_int64(), c.c_double()
+        _chk(lib().ibwa_stdaln_chunks(self.h, c.byref(k), c.byref(ms)))
+        return k.value, ms.value
 
     def sw(self, refs, reads):
         """Batched aln_local_core (stdaln.c:529) over code arrays.  Returns a list of

@@ -501,6 +501,55 @@ int ibwa_cs2nt_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const uint
                      const uint8_t *qual, const uint64_t *off, const uint32_t *len, const int32_t *n_cigar,
                      const uint32_t *cigar, uint8_t *out, uint32_t *new_len);
 
+/*
+ * Batched pairwise alignment with any scoring scheme: aln_local_core (stdaln.c:529-760, with its
+ * suboptimal score) or aln_global_core (stdaln.c:345-525) for a run-time AlnParam, plus
+ * aln_path2cigar32.  What `stdsw` (simple_dp.c) runs per short sequence and strand.
+ *
+ * ibwa_aln_param_t is the reference's AlnParam: gap_open, gap_ext, gap_end, a row x row score matrix
+ * (2 <= row <= 32; the score of codes x of seq2 and y of seq1 is matrix[x * row + y]) and band_width
+ * (<= 0: len1 + len2 of each pair, a full matrix, as stdsw sets it).  ibwa_aln_param_preset fills
+ * one of the presets: "blast" (5 / 2 / 2, +1 / -3, -2 with N, 5 x 5, band 50), "aa2aa" (10 / 2 / 2,
+ * BLOSUM62 over ARNDCQEGHILKMFPSTWYV*X, 22 x 22, band 50) or "bwa" (26 / 9 / 5, 11 / -19 / -13,
+ * 5 x 5, band 50); the matrix points at static storage.
+ *
+ * Pair p aligns seq1[off1[p] .. +len1[p]) (the inner dimension i) with seq2[off2[p] .. +len2[p]) (the
+ * outer loop j, which the suboptimal score is taken over); the codes arrive encoded, each < row.
+ * type 0 (local, _thres = thres >= 1): score (-1 for an empty sequence), subo, path_len (0 when
+ * score < thres: no path, ends and CIGAR then), ends[4p..4p+3] = start i, start j, end i, end j
+ * (1-based: path[path_len-1] and path[0]), n_cigar.  type 1 (global): score, path_len, ends, n_cigar;
+ * subo is 0; an empty sequence gives score 0 and path_len 0.  *cigar = malloc'd concatenation of the
+ * CIGARs (len << 4 | op, op 0 M, 1 I, 2 D; ibwa_free).
+ *
+ * IBWA_EINVAL, with a message that names the offender, for: gap_open or gap_ext < 1, gap_end > 700 or
+ * gap_open + gap_ext > 700; row outside 2..32; a matrix whose maximum is <= 0; a code >= row;
+ * thres < 1 in local mode; local mode with max_score * min(len1, len2) > 32000 (the reference's
+ * rebasing is then unreachable); a length above IBWA_STDALN_MAX_LEN; global mode with more than
+ * IBWA_STDALN_MAX_CELLS cells, (len1 + 1) * (len2 + 1), or in which (len1 + len2) times the largest
+ * score or gap cost reaches 2^30 (the global core's scores are ints beside -2^30); a pair whose
+ * scratch alone is past the per-launch scratch (option "stdaln_scratch_mb", MiB).  The local path
+ * fill's scratch is sized for the longest region a hit can cover, S + (S * max_score + gap_open +
+ * gap_ext) / gap_ext + 1 symbols of a sequence with S = min(len1, len2), so cheap gaps beside large
+ * scores make a pair's scratch large.  A batch larger than the scratch runs in several launches; ibwa_stdaln_chunks tells how many the last call took (and their kernel time).
+ */
+typedef struct {
+	int gap_open, gap_ext, gap_end;
+	const int32_t *matrix;
+	int row, band_width;
+} ibwa_aln_param_t;
+#define IBWA_STDALN_MAX_LEN (4 << 20)
+#define IBWA_STDALN_MAX_CELLS (32ll << 20)
+int ibwa_aln_param_preset(const char *name, ibwa_aln_param_t *ap);
+int ibwa_stdaln_batch(ibwa_ctx_t *ctx, const ibwa_aln_param_t *ap, int type, int thres, int64_t n, const uint8_t *seq1,
+                      const uint64_t *off1, const uint32_t *len1, const uint8_t *seq2, const uint64_t *off2,
+                      const uint32_t *len2, int32_t *score, int32_t *subo, int32_t *path_len, int32_t *ends,
+                      int32_t *n_cigar, uint32_t **cigar, int64_t *n_cigar_total);
+int ibwa_stdaln_chunks(const ibwa_ctx_t *ctx, int64_t *launches, double *kernel_ms);
+/* The parameter and size checks of ibwa_stdaln_batch alone (no device is touched). */
+int ibwa_stdaln_check(const ibwa_aln_param_t *ap, int type, int thres, int64_t n, const uint8_t *seq1,
+                      const uint64_t *off1, const uint32_t *len1, const uint8_t *seq2, const uint64_t *off2,
+                      const uint32_t *len2);
+
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
 

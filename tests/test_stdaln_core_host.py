@@ -1,0 +1,23 @@
+"""stdaln_core.h on the host: the statements the kernel runs (a lane's elements 64 apart) instantiated
+with stride 1 and compared with the compiled reference (oracle/_ref/libibwa_ref.so) on random pairs
+and on pairs with long internal gaps -- tests/host/stdaln_core_check.cpp, built here with g++."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.skipif(not os.path.exists(oracle.REF_LIB) or shutil.which("g++") is None,
+                    reason="needs the compiled reference and g++")
+def test_core_equals_reference_on_host(tmp_path):
+    exe = str(tmp_path / "stdaln_core_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I", os.path.join(ROOT, "ibwa_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "host", "stdaln_core_check.cpp"), "-ldl"], check=True)
+    r = subprocess.run([exe, oracle.REF_LIB, "12000"], stdout=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert r.stdout.strip().endswith("0 differ")
