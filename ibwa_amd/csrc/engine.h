@@ -311,6 +311,36 @@ struct StdArgs {
 };
 hipError_t launch_stdaln(const StdArgs &a, unsigned long long *d_counter, int waves, hipStream_t st);
 
+// Seed extension, aln_extend_core (extend.hip): one launch of a chunk of pairs.
+struct ExtArgs {
+  const uint8_t *seq1, *seq2;     // codes < row
+  const uint64_t *off1, *off2;
+  const uint32_t *len1, *len2;
+  const int32_t *g0;              // null: 1 for every pair
+  int64_t n;
+  int gap_open, gap_ext, band, row, max_score;  // band <= 0: len1 + len2 of each pair
+  const int32_t *matrix;          // row x row, device
+  int mode;                       // 0 score only, 1 end cell, 2 path
+  uint32_t lds_ring;              // words of LDS per lane for the eh ring; a pair whose ring is wider uses the scratch
+  uint32_t *scratch;              // words_per_lane u32 per lane, lane-minor per wave: eh | mid
+  uint64_t words_per_lane;
+  uint32_t e_mid, mid_w;          // first word and cells per row of the (M, I, D) rows (mode 2)
+  uint8_t *tb;                    // tb_per_lane bytes (cells) per lane, lane-minor dwords per wave (mode 2)
+  uint64_t tb_per_lane;
+  int32_t *score, *no_band, *path_len, *n_cigar;
+  int4 *ends;                     // start_i, start_j (mode 2), end_i, end_j
+  uint32_t *cigar;
+  int cigar_cap;
+};
+uint32_t extend_lds_bytes(const ExtArgs &a);
+// all_lds: every pair's ring fits lds_ring words
+hipError_t launch_extend(const ExtArgs &a, bool all_lds, unsigned long long *d_counter, int waves, hipStream_t st);
+// the seeds' target windows from the resident sequence (l bases): dir 0 the bases pos, pos + 1, ...; dir 1
+// pos - 1, pos - 2, ...; len1[p] of them (the host clips) to seq1 + off1[p]; rev: base x is base l - x - 1
+// of the stored sequence (__rpac, bwtsw2_aux.c:78)
+hipError_t launch_extend_gather(const uint32_t *pac, uint64_t l_pac, int rev, int64_t n, const uint64_t *pos, const uint8_t *dir,
+                                const uint64_t *off1, const uint32_t *len1, uint8_t *seq1, hipStream_t st);
+
 // The packed reference in HBM, refinement windows / fix-ups and MD/NM (refine.hip).
 // The resident sequence: the set's references back to back, base g at bits 7-6 .. 1-0 of byte g / 4,
 // in 32-bit words.  launch_pac_concat builds it from the references' own .pac bytes (src, reference

@@ -221,9 +221,11 @@ struct SwBufs {
   DBuf scr, tbb;                // DP scratch, traceback
   DBuf cf, cc;                  // packed CIGARs: each row's first word, the words
 };
-// ibwa_stdaln_batch's buffers (kept between calls).
+// ibwa_stdaln_batch's and ibwa_extend_batch's buffers (kept between calls).  g0 / pos / dir: the
+// extension's G0 per pair and ibwa_extend_seeds' positions and directions.
 struct StdBufs {
   DBuf s1, s2, o1, o2, l1, l2, mat;
+  DBuf g0, pos, dir;
   DBuf sc, su, pl, nc, en, cg;  // score, subo, path_len, n_cigar, ends, a chunk's CIGAR rows
   DBuf scr, tbb, cf, cc;        // DP scratch, traceback, packed CIGARs (first words, words)
 };
@@ -344,6 +346,7 @@ struct ibwa_ctx : ibwa::CtxQueue {
   int64_t stdaln_suba_rows = 8192;   // option: keep suba (one entry per row of seq2) up to this many rows
   int64_t stdaln_chunks = 0;         // launches the last ibwa_stdaln_batch took
   double stdaln_ms = 0;              // ... and their kernel time
+  int64_t extend_no_band = 0;        // path-mode pairs of the last extension whose global fill stayed below the extension score
   int diag = 0;                      // option: keep per-read first-pass iterations and k_width features
   uint32_t gap_stream_per_read = 4;     // first-pass hit-stream slots per read
   uint64_t gap_stream_min = 1u << 20;   // ... and at least this many in total

@@ -1,7 +1,8 @@
-// stdaln_core.h -- aln_local_core (stdaln.c:529-760) and aln_global_core (stdaln.c:345-525) for a
-// run-time AlnParam, one alignment per caller.  The passes are written over strided views of the
-// caller's storage, so that the kernel (stdaln.hip: a lane's elements 64 apart, the eh row in LDS or
-// in HBM) and a host build (stride 1) run the same statements.
+// stdaln_core.h -- aln_local_core (stdaln.c:529-760), aln_global_core (stdaln.c:345-525) and
+// aln_extend_core (stdaln.c:862-1008) for a run-time AlnParam, one alignment per caller.  The passes are
+// written over strided views of the caller's storage, so that the kernels (stdaln.hip, extend.hip: a
+// lane's elements 64 apart, the eh row in LDS or in HBM) and a host build (stride 1) run the same
+// statements.
 #pragma once
 #include <stdint.h>
 
@@ -314,6 +315,159 @@ STD_HD void local_core(const EH &eh, const SUBA &suba, bool keep_suba, const MID
   }
   o.s_i = si + start_i - 1; o.s_j = sj + start_j - 1;
   o.e_i = n1s + start_i - 1; o.e_j = n2s + start_j - 1;
+}
+
+// ---- aln_extend_core (stdaln.c:862-1008)
+constexpr int EXT_OVERFLOW = 32000, EXT_REDUCE = 16000;  // LOCAL_OVERFLOW_THRESHOLD / _REDUCE
+
+// the band a pair runs with: band_width <= 0 is len1 + len2, and nothing wider than that changes a
+// row (start stays 1, end is clipped at len1 + 1), so j + band cannot wrap
+STD_HD int extend_band(int band_width, int n1, int n2) {
+  return (band_width <= 0 || band_width > n1 + n2) ? n1 + n2 : band_width;
+}
+
+// words of the eh ring.  A row reads the cells start .. end, start >= j - band and end <= j + band,
+// and start never decreases: a ring of 2 * band + 2 words holds every cell that is read again
+// (cell i shares its word with i - R < start and i + R > the highest cell touched so far); len1 + 2
+// words is the reference's whole array and never wraps.
+STD_HD uint32_t extend_ring(int band, int n1) {
+  const uint64_t w = 2ull * (uint32_t)band + 2;
+  return (uint32_t)(w < (uint64_t)n1 + 2 ? w : (uint64_t)n1 + 2);
+}
+
+// the rows of seq1 / seq2 the best cell can lie in: a cell (j, i) of the band has i <= j + band - 1
+// and j <= i + band
+STD_HD uint64_t extend_span1(int band, int n1, int n2) {
+  const uint64_t w = (uint64_t)n2 + (uint32_t)band - 1;
+  return w < (uint64_t)n1 ? w : (uint64_t)n1;
+}
+STD_HD uint64_t extend_span2(int band, int n1, int n2) {
+  const uint64_t w = (uint64_t)n1 + (uint32_t)band;
+  return w < (uint64_t)n2 ? w : (uint64_t)n2;
+}
+
+// The extension pass (stdaln.c:901-973): row j over seq2, cell i over seq1, eh[i] = h[j-1,i-1] << 16 |
+// e[j,i] in a ring of R words (extend_ring, or len1 + 2 for the whole array), eh[1] = G0 << 16.  A
+// cell that enters the window for the first time is zeroed there (the reference's memset), so the
+// ring needs no clearing.  band: extend_band().  Returns score + of_base - 1.
+template <class EH>
+STD_HD int extend_fill(const EH &eh, uint32_t R, const Param &P, int band, const uint8_t *a, int n1, const uint8_t *b, int n2,
+                       int G0, int &end_i, int &end_j) {
+  const int r = P.r, qr = P.q + P.r;
+  int start = 1, end = 2, score = 0, of_base = 0;
+  bool is_overflow = false;
+  end_i = end_j = 0;
+  eh[1] = (uint32_t)G0 << 16;  // R >= 3
+  eh[2] = 0;
+  int hw = 2;        // the highest cell initialised
+  uint32_t hwk = 2;  // ... and its word
+  for (int j = 1; j <= n2; ++j) {
+    int h1 = 0, f = 0;
+    const int *srow = P.mat + (int)b[j - 1] * P.row;
+    int s0 = j - band, e0 = j + band;
+    if (s0 < 1) s0 = 1;
+    if (s0 > start) start = s0;
+    if (e0 > n1 + 1) e0 = n1 + 1;
+    if (e0 < end) end = e0;
+    if (start >= end) break;  // ==: the reference's break; >: its row is empty, which ends it as well
+    while (hw < end) {
+      ++hw;
+      if (++hwk == R) hwk = 0;
+      eh[hwk] = 0;
+    }
+    const uint32_t k0 = (uint32_t)start % R;
+    if (is_overflow) {  // stdaln.c:917-930, cells below the reduction clamp to zero
+      score -= EXT_REDUCE;
+      of_base += EXT_REDUCE;
+      is_overflow = false;
+      uint32_t k = k0;
+      for (int i = start; i <= end; ++i) {
+        const uint32_t sv = eh[k];
+        int hh = (int)(sv >> 16), ee = (int)(sv & 0xffff);
+        ee = ee < EXT_REDUCE ? 0 : ee - EXT_REDUCE;
+        hh = hh < EXT_REDUCE ? 0 : hh - EXT_REDUCE;
+        eh[k] = (uint32_t)hh << 16 | (uint32_t)ee;
+        if (++k == R) k = 0;
+      }
+    }
+    int first = 0, lastp = 0;
+    uint32_t k = k0;
+    for (int i = start; i < end; ++i) {
+      const uint32_t sv = eh[k];
+      int h = (int)(sv >> 16), e = (int)(sv & 0xffff);
+      const uint32_t nv = (uint32_t)h1 << 16;
+      h += h ? srow[a[i - 1]] : 0;  // a zero diagonal never restarts
+      h = h > e ? h : e;
+      h = h > f ? h : f;
+      h1 = h;
+      if (h > 0) {
+        if (first == 0) first = i;
+        lastp = i;
+        if (score < h) {
+          score = h; end_i = i; end_j = j;
+          if (score > EXT_OVERFLOW) is_overflow = true;
+        }
+      }
+      h -= qr;
+      h = h > 0 ? h : 0;
+      e -= r;
+      e = e > h ? e : h;
+      f -= r;
+      f = f > h ? f : h;
+      eh[k] = nv | (uint32_t)e;
+      if (++k == R) k = 0;
+    }
+    eh[k] = (uint32_t)h1 << 16;  // cell `end`
+    if (lastp <= 0) break;       // no positive cell in this row
+    start = first;
+    end = lastp + 3;
+  }
+  return score + of_base - 1;
+}
+
+struct ExtOut {
+  int score, end_i, end_j, path_len, n_cig, s_i, s_j, no_band;
+};
+
+// aln_extend_core.  mode 0: the score alone; 1: the end cell (path != 0, path_len == 0); 2: the path, by
+// global alignment of seq1[0, end_i) with seq2[0, end_j), gap_end -1, the band doubling from band_width
+// until the global score equals the extension score or the band passes max(end_i, end_j).  The score
+// returned is then the global one, which leaves G0 out: for G0 > 1 the two never meet, the band runs
+// to the end and no_band is set where the reference prints "no suitable bandwidth".  P.band:
+// extend_band().  W / fill_cells / cap: the widest (M, I, D) row, the traceback cells and the CIGAR
+// words the caller has, sized by extend_span1 / extend_span2.
+template <class EH, class MID, class TB>
+STD_HD void extend_core(const EH &eh, uint32_t R, const MID &mid, uint32_t W, const TB &T, uint64_t fill_cells, const Param &P,
+                        int mode, int G0, const uint8_t *a, int n1, const uint8_t *b, int n2, uint32_t *cig, int cap,
+                        ExtOut &o) {
+  o.score = -1;
+  o.end_i = o.end_j = o.path_len = o.n_cig = o.s_i = o.s_j = o.no_band = 0;
+  if (n1 == 0 || n2 == 0) return;
+  int end_i = 0, end_j = 0;
+  const int score = extend_fill(eh, R, P, P.band, a, n1, b, n2, G0, end_i, end_j);
+  o.score = score;
+  if (score <= 0 || mode == 0) return;
+  o.end_i = end_i; o.end_j = end_j;
+  if (mode == 1) return;
+  // memory guard: the host sizes W, fill_cells and cap for the band's reach
+  if ((uint32_t)end_i + 1 > W || (uint64_t)(end_i + 1) * (uint64_t)(end_j + 1) > fill_cells || end_i + end_j > cap) {
+    o.score = REFUSED;
+    return;
+  }
+  const int jmax = end_i > end_j ? end_i : end_j;
+  int score_g = 0;
+  for (int bw = P.band;; bw <<= 1) {
+    score_g = global_core(mid, W, T, P, a, end_i, b, end_j, bw, -1, cig, cap, o.n_cig, o.path_len, o.s_i, o.s_j);
+    if (score == score_g) break;
+    if (bw > jmax) break;
+  }
+  if (score > score_g) o.no_band = 1;
+  o.score = score_g;
+  for (int k = 0; k < o.n_cig / 2; ++k) {
+    const uint32_t t = cig[k];
+    cig[k] = cig[o.n_cig - 1 - k];
+    cig[o.n_cig - 1 - k] = t;
+  }
 }
 
 }  // namespace stdaln

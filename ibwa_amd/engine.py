@@ -140,6 +140,11 @@ CAPI = {
                                c.POINTER(c.c_void_p), c.POINTER(_i64)]),
     "ibwa_stdaln_check": (_i, [_vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_stdaln_chunks": (_i, [_vp, c.POINTER(_i64), c.POINTER(c.c_double)]),
+    "ibwa_extend_batch": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               c.POINTER(c.c_void_p), c.POINTER(_i64)]),
+    "ibwa_extend_check": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_extend_seeds": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_extend_stats": (_i, [_vp, c.POINTER(_i64)]),
     "ibwa_ctx_load_pac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
     "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
@@ -230,12 +235,35 @@ def _pair_arrays(seq1s, seq2s):
     return n, s1, o1, l1, s2, o2, l2
 
 
+_STDALN_TYPES = {"local": 0, "global": 1, "extend": 2}
+_EXTEND_MODES = {"score": 0, "end": 1, "path": 2}
+
+
 def stdaln_check(seq1s, seq2s, param, mode="local", thres=1):
     """The checks of ibwa_stdaln_batch alone (no device): raises IbwaError on a refusal."""
     ap, _mat = _aln_param_struct(param)
     n, s1, o1, l1, s2, o2, l2 = _pair_arrays(seq1s, seq2s)
-    _chk(lib().ibwa_stdaln_check(c.byref(ap), {"local": 0, "global": 1}[mode], thres, n, s1.ctypes.data, o1.ctypes.data,
+    _chk(lib().ibwa_stdaln_check(c.byref(ap), _STDALN_TYPES[mode], thres, n, s1.ctypes.data, o1.ctypes.data,
                                  l1.ctypes.data, s2.ctypes.data, o2.ctypes.data, l2.ctypes.data))
+
+
+def _g0_array(g0, n):
+    """One G0 for every pair or one per pair -> int32[n] (None: the library's default of 1)."""
+    if g0 is None:
+        return None
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(g0, dtype=np.int64), (n,)))
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise IbwaError("extend: a G0 does not fit 32 bits")
+    return a.astype(np.int32)
+
+
+def extend_check(seq1s, seq2s, param, g0=1, mode="end"):
+    """The checks of ibwa_extend_batch alone (no device): raises IbwaError on a refusal."""
+    ap, _mat = _aln_param_struct(param)
+    n, s1, o1, l1, s2, o2, l2 = _pair_arrays(seq1s, seq2s)
+    g = _g0_array(g0, n)
+    _chk(lib().ibwa_extend_check(c.byref(ap), _EXTEND_MODES[mode], n, s1.ctypes.data, o1.ctypes.data, l1.ctypes.data,
+                                 s2.ctypes.data, o2.ctypes.data, l2.ctypes.data, None if g is None else g.ctypes.data))
 
 
 def default_opt():
@@ -515,7 +543,8 @@ class Engine:
         return out
 
     def stdaln(self, seq1s, seq2s, param, mode="local", thres=1):
-        """Batched aln_local_core / aln_global_core for any scoring scheme (ibwa_stdaln_batch).
+        """Batched aln_local_core / aln_global_core / aln_extend_core (mode "local", "global", "extend": the
+        last is aln_stdaln_aux's type 2, G0 = 1 with the path) for any scoring scheme (ibwa_stdaln_batch).
         seq1s / seq2s: code arrays (each code < row); param: a preset name, aln_param()'s dict, or a
         (gap_open, gap_ext, gap_end, matrix, row, band_width) tuple (band_width <= 0: len1 + len2).
         Returns per pair (score, subo, path_len, start (i, j) | None, end (i, j) | None, cigar str |
@@ -529,7 +558,7 @@ class Engine:
         ncig = np.zeros(n, np.int32)
         ptr = c.c_void_p()
         tot = c.c_int64()
-        _chk(lib().ibwa_stdaln_batch(self.h, c.byref(ap), {"local": 0, "global": 1}[mode], thres, n, s1.ctypes.data,
+        _chk(lib().ibwa_stdaln_batch(self.h, c.byref(ap), _STDALN_TYPES[mode], thres, n, s1.ctypes.data,
                                      o1.ctypes.data, l1.ctypes.data, s2.ctypes.data, o2.ctypes.data, l2.ctypes.data,
                                      score.ctypes.data, subo.ctypes.data, plen.ctypes.data, ends.ctypes.data,
                                      ncig.ctypes.data, c.byref(ptr), c.byref(tot)))
@@ -551,6 +580,69 @@ class Engine:
         k, ms = c.c_int64(), c.c_double()
         _chk(lib().ibwa_stdaln_chunks(self.h, c.byref(k), c.byref(ms)))
         return k.value, ms.value
+
+    def extend(self, seq1s, seq2s, param, g0=1, mode="end"):
+        """Batched aln_extend_core (ibwa_extend_batch).  g0: one value or one per pair.  Returns per pair
+        (score, end (i, j) | None) in mode "end", (score, None) in mode "score", and (score, end | None,
+        path_len, cigar str | None) in mode "path" (score: the global fill's, as the reference returns it)."""
+        ap, _mat = _aln_param_struct(param)
+        n, s1, o1, l1, s2, o2, l2 = _pair_arrays(seq1s, seq2s)
+        g = _g0_array(g0, n)
+        m = _EXTEND_MODES[mode]
+        score = np.zeros(n, np.int32)
+        ends = np.zeros((n, 2), np.int32)
+        plen = np.zeros(n, np.int32)
+        ncig = np.zeros(n, np.int32)
+        ptr = c.c_void_p()
+        tot = c.c_int64()
+        _chk(lib().ibwa_extend_batch(self.h, c.byref(ap), m, n, s1.ctypes.data, o1.ctypes.data, l1.ctypes.data,
+                                     s2.ctypes.data, o2.ctypes.data, l2.ctypes.data, None if g is None else g.ctypes.data,
+                                     score.ctypes.data, ends.ctypes.data, plen.ctypes.data, ncig.ctypes.data,
+                                     c.byref(ptr), c.byref(tot)))
+        cig = np.zeros(0, np.uint32)
+        if ptr.value:
+            cig = np.frombuffer(c.string_at(ptr.value, 4 * max(tot.value, 0)), dtype=np.uint32).copy()
+            lib().ibwa_free(ptr)
+        out, q = [], 0
+        for p in range(n):
+            has_end = score[p] > 0 if m == 1 else plen[p] > 0  # path mode: the global score may be <= 0 beside a path
+            end = (int(ends[p, 0]), int(ends[p, 1])) if has_end else None
+            if m < 2:
+                out.append((int(score[p]), end))
+            elif plen[p] > 0:
+                out.append((int(score[p]), end, int(plen[p]),
+                            "".join(f"{x >> 4}{'MIDS'[x & 0xf]}" for x in cig[q:q + ncig[p]])))
+            else:
+                out.append((int(score[p]), None, 0, None))
+            q += ncig[p]
+        return out
+
+    def extend_seeds(self, pos, dirs, lts, queries, param, g0=1, rev=False):
+        """End-cell extension of seeds against the resident sequence (ibwa_extend_seeds): seed p reads at most
+        lts[p] bases rightwards from pos[p] (dirs[p] == 0) or leftwards from pos[p] - 1 (dirs[p] == 1);
+        queries[p]: the codes in the order the DP consumes them.  Returns per seed (score, end (i, j) | None)."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64)
+        dirs = np.ascontiguousarray(dirs, dtype=np.uint8)
+        lts = np.ascontiguousarray(lts, dtype=np.uint32)
+        n = len(queries)
+        if not (pos.size == dirs.size == lts.size == n):
+            raise IbwaError("extend_seeds: pos, dirs, lts and queries differ in length")
+        ap, _mat = _aln_param_struct(param)
+        s, off, ln = self._pack_reads(queries)
+        g = _g0_array(g0, n)
+        score = np.zeros(n, np.int32)
+        ends = np.zeros((n, 2), np.int32)
+        _chk(lib().ibwa_extend_seeds(self.h, c.byref(ap), n, pos.ctypes.data, dirs.ctypes.data, lts.ctypes.data, int(bool(rev)),
+                                     s.ctypes.data, off.ctypes.data, ln.ctypes.data, None if g is None else g.ctypes.data,
+                                     score.ctypes.data, ends.ctypes.data))
+        return [(int(score[p]), (int(ends[p, 0]), int(ends[p, 1])) if score[p] > 0 else None) for p in range(n)]
+
+    def extend_stats(self):
+        """{"no_band": path-mode pairs of the last extension whose global fill stayed below the extension
+        score (the reference's 'no suitable bandwidth' line)}."""
+        k = c.c_int64()
+        _chk(lib().ibwa_extend_stats(self.h, c.byref(k)))
+        return {"no_band": k.value}
 
     def sw(self, refs, reads):
         """Batched aln_local_core (stdaln.c:529) over code arrays.  Returns a list of

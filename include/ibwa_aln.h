@@ -518,7 +518,8 @@ int ibwa_cs2nt_batch(ibwa_ctx_t *ctx, int64_t n, const uint64_t *pos, const uint
  * type 0 (local, _thres = thres >= 1): score (-1 for an empty sequence), subo, path_len (0 when
  * score < thres: no path, ends and CIGAR then), ends[4p..4p+3] = start i, start j, end i, end j
  * (1-based: path[path_len-1] and path[0]), n_cigar.  type 1 (global): score, path_len, ends, n_cigar;
- * subo is 0; an empty sequence gives score 0 and path_len 0.  *cigar = malloc'd concatenation of the
+ * subo is 0; an empty sequence gives score 0 and path_len 0.  type 2 (extend): see ibwa_extend_batch
+ * below.  *cigar = malloc'd concatenation of the
  * CIGARs (len << 4 | op, op 0 M, 1 I, 2 D; ibwa_free).
  *
  * IBWA_EINVAL, with a message that names the offender, for: gap_open or gap_ext < 1, gap_end > 700 or
@@ -549,6 +550,56 @@ int ibwa_stdaln_chunks(const ibwa_ctx_t *ctx, int64_t *launches, double *kernel_
 int ibwa_stdaln_check(const ibwa_aln_param_t *ap, int type, int thres, int64_t n, const uint8_t *seq1,
                       const uint64_t *off1, const uint32_t *len1, const uint8_t *seq2, const uint64_t *off2,
                       const uint32_t *len2);
+
+/*
+ * Seed extension: aln_extend_core (stdaln.c:862-1008) for a run-time AlnParam, batched.  Pair p extends
+ * from the corner cell with the score g0[p] (NULL: 1 for every pair) into seq1[off1[p] .. +len1[p]) (the
+ * inner dimension i) and seq2[off2[p] .. +len2[p]) (the rows j) inside the reference's adaptive band;
+ * a zero cell never restarts.  The score is what aln_extend_core returns: best cell + rebasing - 1, -1
+ * for an empty sequence; past 32000 the rows are rebased by 16000 as at stdaln.c:917-930.
+ * band_width <= 0 is len1 + len2 of each pair, this library's convention (the reference takes the
+ * number as it is: its first row is then empty, or its row bounds leave the array).
+ *   mode 0  the score alone.
+ *   mode 1  the end cell: ends[2p], ends[2p + 1] = end_i, end_j of the first best cell in row-major order
+ *           (0, 0 when score <= 0).  What bsw2_extend_left / _rght use (bwtsw2_aux.c:80-164).
+ *   mode 2  the path: aln_global_core over seq1[0, end_i) x seq2[0, end_j) with gap_end -1, the band
+ *           doubling from band_width until the global score equals the extension score or the band
+ *           passes max(end_i, end_j); score = that global score, which leaves g0 out (so for g0 > 1
+ *           the band always runs to the end); path_len, n_cigar, *cigar as ibwa_stdaln_batch gives them.
+ *           Where the reference prints "no suitable bandwidth" the pair is counted: ibwa_extend_stats.
+ * path_len / n_cigar / cigar may be NULL in modes 0 and 1.  ibwa_stdaln_batch with type 2 is
+ * aln_stdaln_aux's ALN_TYPE_EXTEND: g0 = 1, mode 2, subo = 0, ends[4p..] = the path's first and last cell.
+ *
+ * IBWA_EINVAL, with a message that names the pair, for ibwa_stdaln_batch's parameter checks, g0 outside
+ * 1..32000, a code >= row, a length above IBWA_STDALN_MAX_LEN, and in mode 2 a pair whose path fill can
+ * pass IBWA_STDALN_MAX_CELLS or the per-launch scratch; end_i <= len2 + band - 1 and end_j <= len1 + band
+ * bound the fill.  A batch larger than the scratch runs in several launches (ibwa_stdaln_chunks).
+ *
+ * ibwa_extend_seeds: mode 1 with the targets read on the device from ibwa_ctx_load_pac's sequence (no
+ * target byte crosses the bus).  Seed p, dir[p] == 0 (right): the bases pos[p], pos[p] + 1, ..., at most
+ * lt[p] of them, clipped at the set's total length l.  dir[p] == 1 (left): pos[p] - 1, pos[p] - 2, ...,
+ * at most lt[p], ending with base 0 at the latest; bsw2_extend_left's loop never takes base 0, so to
+ * match it pass lt = min(lt, pos - 1).  rev != 0 reads base x as __rpac does (bwtsw2_aux.c:78): base
+ * l - x - 1 of the stored sequence, reversed and not complemented.  qry[off[p] .. +len[p]) is the
+ * query slice in the orientation the DP consumes it (for a left extension the reversed prefix, as
+ * bsw2_extend_left builds it).  The windows may run from one reference of the set into the next.
+ * IBWA_ENOINDEX while no sequence is loaded; an empty window gives score -1; a left seed with
+ * pos > l, a dir above 1 or row < 4 is IBWA_EINVAL.  Sorting hits and the containment test of
+ * bsw2_extend_left are the caller's.
+ */
+int ibwa_extend_batch(ibwa_ctx_t *ctx, const ibwa_aln_param_t *ap, int mode, int64_t n, const uint8_t *seq1,
+                      const uint64_t *off1, const uint32_t *len1, const uint8_t *seq2, const uint64_t *off2,
+                      const uint32_t *len2, const int32_t *g0, int32_t *score, int32_t *ends, int32_t *path_len,
+                      int32_t *n_cigar, uint32_t **cigar, int64_t *n_cigar_total);
+/* The parameter and size checks of ibwa_extend_batch alone (no device is touched). */
+int ibwa_extend_check(const ibwa_aln_param_t *ap, int mode, int64_t n, const uint8_t *seq1, const uint64_t *off1,
+                      const uint32_t *len1, const uint8_t *seq2, const uint64_t *off2, const uint32_t *len2,
+                      const int32_t *g0);
+int ibwa_extend_seeds(ibwa_ctx_t *ctx, const ibwa_aln_param_t *ap, int64_t n, const uint64_t *pos, const uint8_t *dir,
+                      const uint32_t *lt, int rev, const uint8_t *qry, const uint64_t *off, const uint32_t *len,
+                      const int32_t *g0, int32_t *score, int32_t *ends);
+/* path-mode pairs of the last extension call whose global fill stayed below the extension score */
+int ibwa_extend_stats(const ibwa_ctx_t *ctx, int64_t *no_band);
 
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
