@@ -422,6 +422,32 @@ hipError_t derive_sampled_sa(const IndexView &ix, uint32_t intv, uint32_t *sa_s,
 hipError_t derive_isa_text(const IndexView &ix, const uint32_t *full, uint32_t *isa, uint32_t *txt2, uint64_t txt_words,
                            hipStream_t st);
 
+// bwasw's seeding (seed.hip): bsw2_core per task, one task per persistent wave.
+struct SeedArgs {
+  IndexView ix[2];           // ix[0] = .bwt, ix[1] = .rbwt
+  const uint32_t *sa[2];     // sampled or full SA of each index
+  uint32_t intv[2];          // its sampling interval (1: full)
+  const uint8_t *seq;        // codes 0-3
+  const uint64_t *off;
+  const uint32_t *len;
+  const uint8_t *strand;     // which index a task searches
+  const int32_t *t, *bw;     // per task, already derived from its length
+  const int64_t *ids;        // the tasks to run (a retry launch), or null for tasks 0 .. n - 1
+  int64_t n;
+  int a, b, q, r, z, is;
+  uint32_t *arena;           // one range of arena_words words per workgroup
+  uint64_t arena_words;
+  uint32_t *res;             // per task 8 words: status (0 ok, 1 arena, 2 output full), rows of the all-array
+                             // to sort and those with G > 0, the same for the narrow array, first output
+                             // record (2 words), arena words used
+  uint32_t *out;             // ibwa_bsw2_hit_t records (l: the row's place in the array to sort)
+  unsigned long long *out_next;
+  unsigned long long out_cap;  // records
+  unsigned long long *claim;
+  unsigned long long *prof;  // 4 words: wall-clock ticks of bwtl build, traversal, resolve; cells visited
+};
+hipError_t launch_seed(const SeedArgs &a, int blocks, hipStream_t st);
+
 hipError_t build_kmer_table(const IndexView &ix, int K, uint2 *table, uint2 *tmp, hipStream_t st);
 // first index of level d of a level table: (4^d - 1) / 3 rounded up to a multiple of 4 (level d >= 1 then
 // starts 32 B-aligned, so a node's four children are one aligned 32 B load)

@@ -229,6 +229,10 @@ struct StdBufs {
   DBuf sc, su, pl, nc, en, cg;  // score, subo, path_len, n_cigar, ends, a chunk's CIGAR rows
   DBuf scr, tbb, cf, cc;        // DP scratch, traceback, packed CIGARs (first words, words)
 };
+// ibwa_bsw2_seed_batch's buffers (kept between calls).
+struct SeedBufs {
+  DBuf seq, off, len, strand, t, bw, ids, arena, res, out, ctr;
+};
 // ibwa_refine_batch's own buffers.  ibwa_pac_extract borrows them for its begins, lengths and got
 // counts (dpos, dext, dout in that order).
 struct RefineBufs {
@@ -264,6 +268,7 @@ struct ibwa_ctx : ibwa::CtxQueue {
   // post-alignment services
   ibwa::SwBufs sw;
   ibwa::StdBufs sd;
+  ibwa::SeedBufs seed;
   ibwa::RefineBufs rf;
   ibwa::MdBufs md;
   ibwa::CsBufs cs;
@@ -346,6 +351,9 @@ struct ibwa_ctx : ibwa::CtxQueue {
   int64_t stdaln_suba_rows = 8192;   // option: keep suba (one entry per row of seq2) up to this many rows
   int64_t stdaln_chunks = 0;         // launches the last ibwa_stdaln_batch took
   double stdaln_ms = 0;              // ... and their kernel time
+  int64_t seed_arena_cells = 0;      // option: cells of a task's arena in k_bsw2_seed's first launch (0: by read length)
+  int seed_waves_per_cu = 8;         // option: its persistent waves per CU (18 KiB of LDS each)
+  int64_t seed_stats[8] = {};        // ibwa_bsw2_seed_stats
   int64_t extend_no_band = 0;        // path-mode pairs of the last extension whose global fill stayed below the extension score
   int diag = 0;                      // option: keep per-read first-pass iterations and k_width features
   uint32_t gap_stream_per_read = 4;     // first-pass hit-stream slots per read

@@ -35,7 +35,8 @@ class RunStats(c.Structure):
                 ("n_resumed", c.c_int64), ("resume_records", c.c_int64),
                 ("resume_records_peak", c.c_int64), ("resume_records_cap", c.c_int64),
                 ("coop_pages_peak", c.c_int64), ("coop_pages_cap", c.c_int64), ("ms_alloc", c.c_double),
-                ("n_tail_jumps", c.c_int64), ("n_width_tab_steps", c.c_int64)]
+                ("n_tail_jumps", c.c_int64), ("n_width_tab_steps", c.c_int64),
+                ("ms_bsw2_seed", c.c_double), ("n_bsw2_retry", c.c_int64), ("bsw2_arena_peak", c.c_int64)]
 
 
 class RefSeq(c.Structure):
@@ -145,6 +146,11 @@ CAPI = {
     "ibwa_extend_check": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_extend_seeds": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_extend_stats": (_i, [_vp, c.POINTER(_i64)]),
+    "ibwa_bsw2_opt_preset": (_i, [c.c_char_p, _vp]),
+    "ibwa_bsw2_seed_batch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
+    "ibwa_bsw2_seed_check": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "ibwa_bsw2_opt_for_len": (None, [_vp, _u32, c.POINTER(c.c_int32), c.POINTER(c.c_int32)]),
+    "ibwa_bsw2_seed_stats": (_i, [_vp, c.POINTER(c.c_int64 * 8)]),
     "ibwa_ctx_load_pac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
     "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
@@ -233,6 +239,52 @@ def _pair_arrays(seq1s, seq2s):
     s1 = np.concatenate([np.asarray(x, np.uint8) for x in seq1s] + [np.zeros(1, np.uint8)])
     s2 = np.concatenate([np.asarray(x, np.uint8) for x in seq2s] + [np.zeros(1, np.uint8)])
     return n, s1, o1, l1, s2, o2, l2
+
+
+class Bsw2Opt(c.Structure):
+    """ibwa_bsw2_opt_t: what bsw2_aln receives (t and coef scaled by a), and whether t and bw follow the read length."""
+    _fields_ = [(n, c.c_int32) for n in ("a", "b", "q", "r", "t", "bw", "z", "is_")] + \
+               [("coef", c.c_float), ("adjust", c.c_int32)]
+
+
+BSW2_HIT_DTYPE = np.dtype([("k", "<u4"), ("l", "<u4"), ("flag", "<u4"), ("len", "<i4"), ("G", "<i4"), ("G2", "<i4"),
+                           ("beg", "<i4"), ("end", "<i4")])  # ibwa_bsw2_hit_t
+BSW2_MAX_LEN = 8192
+
+
+def bsw2_opt(opt="bwasw", adjust=None, **kw):
+    """A preset name ("bwasw": bsw2_init_opt's defaults), a dict with the keys a b q r t bw z is coef
+    (missing ones from the preset) or a Bsw2Opt -> Bsw2Opt; keywords override, `is` spelled is_ or is."""
+    if isinstance(opt, Bsw2Opt):
+        o = Bsw2Opt.from_buffer_copy(opt)
+    else:
+        o = Bsw2Opt()
+        _chk(lib().ibwa_bsw2_opt_preset((opt if isinstance(opt, str) else "bwasw").encode(), c.byref(o)))
+        if isinstance(opt, dict):
+            kw = dict(opt, **kw)
+    for k, v in kw.items():
+        setattr(o, "is_" if k == "is" else k, v)
+    if adjust is not None:
+        o.adjust = 1 if adjust else 0
+    return o
+
+
+def bsw2_opt_for_len(opt, length):
+    """(t, bw) of a read of that length, bwtsw2_aux.c:483-497."""
+    o = bsw2_opt(opt)
+    t, bw = c.c_int32(), c.c_int32()
+    lib().ibwa_bsw2_opt_for_len(c.byref(o), int(length), c.byref(t), c.byref(bw))
+    return t.value, bw.value
+
+
+def bsw2_seed_check(seqs, strands, opt="bwasw", adjust=None):
+    """The checks of ibwa_bsw2_seed_batch alone (no device): raises IbwaError on a refusal."""
+    o = bsw2_opt(opt, adjust)
+    s, off, ln = Engine._pack_reads(seqs)
+    st = np.ascontiguousarray(strands, dtype=np.uint8)
+    if st.size != ln.size:
+        raise IbwaError("bsw2 seed: seqs and strands differ in length")
+    _chk(lib().ibwa_bsw2_seed_check(c.byref(o), ln.size, s.ctypes.data, off.ctypes.data, ln.ctypes.data, st.ctypes.data))
 
 
 _STDALN_TYPES = {"local": 0, "global": 1, "extend": 2}
@@ -636,6 +688,44 @@ class Engine:
                                      s.ctypes.data, off.ctypes.data, ln.ctypes.data, None if g is None else g.ctypes.data,
                                      score.ctypes.data, ends.ctypes.data))
         return [(int(score[p]), (int(ends[p, 0]), int(ends[p, 1])) if score[p] > 0 else None) for p in range(n)]
+
+    def bwasw_seeds(self, seqs, strands, opt="bwasw", adjust=True):
+        """bwasw's seeding (ibwa_bsw2_seed_batch): bsw2_core of every task -- seqs[i], codes 0-3, against
+        .bwt / .sa (strands[i] == 0) or .rbwt / .rsa (1).  opt: see bsw2_opt; adjust: t and bw follow each
+        read's length as in bsw2_aln_core.  Returns per task (all_hits, narrow_hits), lists of
+        (k, l, flag, len, G, G2, beg, end) tuples in the reference's order after bsw2_resolve_duphits."""
+        o = bsw2_opt(opt, adjust)
+        s, off, ln = self._pack_reads(seqs)
+        st = np.ascontiguousarray(strands, dtype=np.uint8)
+        n = ln.size
+        if st.size != n:
+            raise IbwaError("bsw2 seed: seqs and strands differ in length")
+        n_all = np.zeros(n, np.int32)
+        n_nar = np.zeros(n, np.int32)
+        ptr = c.c_void_p()
+        tot = c.c_int64()
+        _chk(lib().ibwa_bsw2_seed_batch(self.h, c.byref(o), n, s.ctypes.data, off.ctypes.data, ln.ctypes.data,
+                                        st.ctypes.data, n_all.ctypes.data, n_nar.ctypes.data, c.byref(ptr), c.byref(tot)))
+        try:
+            buf = (c.c_char * (tot.value * BSW2_HIT_DTYPE.itemsize)).from_address(ptr.value) if tot.value else b""
+            hits = [tuple(int(x) for x in h) for h in np.frombuffer(buf, dtype=BSW2_HIT_DTYPE).tolist()]
+        finally:
+            lib().ibwa_free(ptr)
+        out, at = [], 0
+        for i in range(n):
+            a, b = int(n_all[i]), int(n_nar[i])
+            out.append((hits[at:at + a], hits[at + a:at + a + b]))
+            at += a + b
+        return out
+
+    def seed_stats(self):
+        """The last bwasw_seeds call: wall-clock ticks its waves spent in bwtl build, traversal and resolve,
+        cells visited, tasks run again, the largest arena a task used and the first launch's arena (bytes),
+        and its workgroups."""
+        v = (c.c_int64 * 8)()
+        _chk(lib().ibwa_bsw2_seed_stats(self.h, c.byref(v)))
+        return dict(zip(("ticks_build", "ticks_walk", "ticks_resolve", "cells", "retried", "arena_peak", "arena",
+                         "workgroups"), [int(x) for x in v]))
 
     def extend_stats(self):
         """{"no_band": path-mode pairs of the last extension whose global fill stayed below the extension

@@ -221,6 +221,9 @@ typedef struct {
 	int64_t n_width_tab_steps;   /* steps k_width's chains took from a level-table entry after a reset
 	                                ("width_tab" 2; 0 when the option or the tables are off), summed over
 	                                the run's k_width launches */
+	double ms_bsw2_seed;         /* last ibwa_bsw2_seed_batch: k_bsw2_seed kernel time, its retry launch included */
+	int64_t n_bsw2_retry;        /* ... tasks that outgrew their arena or the output buffer and ran again */
+	int64_t bsw2_arena_peak;     /* ... the largest arena a task used, in bytes */
 } ibwa_run_stats_t;
 int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
 
@@ -285,6 +288,9 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *                                  barrier and the commit (0: after them); same hits either way
  *   "sa_walk" (0/1, default 0)     SA -> coordinate by walking the sampled SA even when the full SA is
  *                                  resident
+ *   "seed_arena_cells" (0), "seed_waves_per_cu" (8)  ibwa_bsw2_seed_batch: cells (64 B) of a task's arena in
+ *                                  the first launch (0: from the read length; a task that does
+ *                                  not fit runs again in a larger arena) and its persistent waves per CU
  *   Test and diagnostics hooks: "gap_stream_per_read" (4), "gap_stream_min" (1 << 20) the first
  *   pass's hit-stream size; "gap_resume_records", "coop_pool_pages" buffer sizes in records / pages;
  *   "diag" (0) per-read iterations and k_width features; "diag_width" (0) keep the first-pass
@@ -600,6 +606,50 @@ int ibwa_extend_seeds(ibwa_ctx_t *ctx, const ibwa_aln_param_t *ap, int64_t n, co
                       const int32_t *g0, int32_t *score, int32_t *ends);
 /* path-mode pairs of the last extension call whose global fill stayed below the extension score */
 int ibwa_extend_stats(const ibwa_ctx_t *ctx, int64_t *no_band);
+
+/*
+ * bwasw's seeding: bsw2_core (bwtsw2_core.c:429-594) on the read's bwtl (bwt_lite.c:9-54), batched.
+ *
+ * Task i is seq[off[i] .. off[i] + len[i]), codes 0-3, searched against .bwt / .sa when strand[i] == 0 and
+ * against .rbwt / .rsa when it is 1 (bsw2_aln_core's second pass takes the reversed read there).  opt is what
+ * bsw2_aln receives, t and coef already scaled by a (bwtsw2_main.c:82-83).  With adjust != 0 each task's t
+ * and bw are derived from its length as bsw2_aln_core does (bwtsw2_aux.c:483-497; ibwa_bsw2_opt_for_len);
+ * with adjust == 0 they are used as given.
+ *
+ * *hits = malloc'd (ibwa_free): per task the n_all[i] hits of b_ret[0], then the n_narrow[i] hits of
+ * b_ret[1], each list in the reference's final order after bsw2_resolve_duphits, so l == 0, k is a
+ * coordinate (bwt_sa) and flag & 1 marks a repetitive hit.  bsw2hit_t's n_seeds is not part of the
+ * contract (the reference leaves it unset for narrow hits).  With is == 0 and no hit the reference reads
+ * a hit it never allocated; here such a list is empty.
+ *
+ * The traversal, the read's BWT and the bwt_sa lookups run on the device (k_bsw2_seed, one task per
+ * wavefront, each in an arena of HBM); the unstable sort and the containment pass of
+ * bsw2_resolve_duphits run on the host.  A task that outgrows its arena runs once more in a larger one;
+ * IBWA_EOVERFLOW, naming the first such task, if it still does not fit.
+ *
+ * IBWA_ENOINDEX without the index or the suffix array of a strand a task names.  IBWA_EINVAL, with a
+ * message that names the task, for a code >= 4, a strand above 1, a length of 0 or above
+ * IBWA_BSW2_MAX_LEN; and for a, b, q, r or z < 1, is < 0, and t < 1 or bw < 1 with adjust == 0.
+ * n == 0 returns 0 with no hits.  Options: "seed_arena_cells" (0: by read length) the first launch's
+ * cells per task arena, "seed_waves_per_cu" (8).
+ */
+#define IBWA_BSW2_MAX_LEN 8192
+typedef struct { int32_t a, b, q, r, t, bw, z, is; float coef; int32_t adjust; } ibwa_bsw2_opt_t;
+typedef struct { uint32_t k, l, flag; int32_t len, G, G2, beg, end; } ibwa_bsw2_hit_t;   /* bsw2hit_t without n_seeds */
+/* bsw2_init_opt's values for "bwasw" (adjust = 1); IBWA_EINVAL for another name */
+int ibwa_bsw2_opt_preset(const char *name, ibwa_bsw2_opt_t *opt);
+int ibwa_bsw2_seed_batch(ibwa_ctx_t *ctx, const ibwa_bsw2_opt_t *opt, int64_t n, const uint8_t *seq,
+                         const uint64_t *off, const uint32_t *len, const uint8_t *strand,
+                         int32_t *n_all, int32_t *n_narrow, ibwa_bsw2_hit_t **hits, int64_t *n_hits_total);
+/* The checks of ibwa_bsw2_seed_batch alone (no device is touched). */
+int ibwa_bsw2_seed_check(const ibwa_bsw2_opt_t *opt, int64_t n, const uint8_t *seq, const uint64_t *off,
+                         const uint32_t *len, const uint8_t *strand);
+/* t and bw of a read of length len (bwtsw2_aux.c:483-497) */
+void ibwa_bsw2_opt_for_len(const ibwa_bsw2_opt_t *opt, uint32_t len, int32_t *t, int32_t *bw);
+/* The last ibwa_bsw2_seed_batch: out[0..2] wall-clock ticks its waves spent building bwtls, traversing and
+ * resolving, out[3] cells visited, out[4] tasks run again, out[5] the largest arena a task used (bytes),
+ * out[6] the first launch's arena per task (bytes), out[7] its workgroups. */
+int ibwa_bsw2_seed_stats(const ibwa_ctx_t *ctx, int64_t out[8]);
 
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
