@@ -172,12 +172,15 @@ int ibwa_bsw2_seed_batch(ibwa_ctx_t *c, const ibwa_bsw2_opt_t *opt, int64_t n, c
     const int64_t blocks = std::max<int64_t>(
         1, std::min<int64_t>({m, (int64_t)c->n_cus * c->seed_waves_per_cu, (int64_t)((32ull << 30) / (arena_words * 4))}));
     // output records (32 B): the narrow hits dominate, about one per base at z = 1 and ten at z = 10 on the
-    // golden vectors; the launch shares one buffer, and the retry launch has 16 times the room
+    // golden vectors; the launch shares one buffer.  In the retry launch a task that ended
+    // with status 2 gets the rows it counted itself (res[2] + res[4], exact: it resolved both lists
+    // before it asked for room), a task that outgrew its arena 16 times the first launch's share
     const uint64_t per_base = 2 + 2 * (uint64_t)std::min(opt->z, 8);
     uint64_t out_cap = 4096;
     if (pass == 0) out_cap += (uint64_t)n * 64 + len_sum * per_base;
     else
-      for (int64_t i : todo) out_cap += 16 * (64 + len[i] * per_base);
+      for (int64_t i : todo)
+        out_cap += res[i * 8] == 2 ? (uint64_t)res[i * 8 + 2] + res[i * 8 + 4] : 16 * (64 + len[i] * per_base);
     if ((rc = B.arena.ensure((uint64_t)blocks * arena_words * 4)) || (rc = B.out.ensure(out_cap * 32))) return rc;
     a.arena = B.arena.as<uint32_t>();
     a.arena_words = arena_words;

@@ -625,7 +625,11 @@ int ibwa_extend_stats(const ibwa_ctx_t *ctx, int64_t *no_band);
  * The traversal, the read's BWT and the bwt_sa lookups run on the device (k_bsw2_seed, one task per
  * wavefront, each in an arena of HBM); the unstable sort and the containment pass of
  * bsw2_resolve_duphits run on the host.  A task that outgrows its arena runs once more in a larger one;
- * IBWA_EOVERFLOW, naming the first such task, if it still does not fit.
+ * IBWA_EOVERFLOW, naming the first such task, if it still does not fit.  A task whose hits do not fit
+ * the launch's output buffer has counted them, and runs once more with room for exactly that count:
+ * a batch in which no task outgrows its arena never ends in IBWA_EOVERFLOW.  (A task that did outgrow
+ * it has no count; it gets 16 times its planned room, and if it needs more, it or a task that claims
+ * room after it is the one named.)
  *
  * IBWA_ENOINDEX without the index or the suffix array of a strand a task names.  IBWA_EINVAL, with a
  * message that names the task, for a code >= 4, a strand above 1, a length of 0 or above

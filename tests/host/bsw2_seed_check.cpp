@@ -7,8 +7,9 @@
 //       "n_all n_narrow hit..." (hit = k,l,flag,len,G,G2,beg,end), a tab, and the counters.
 //       With threads > 0 nothing is printed but the wall time (the bench's host baseline).
 //   bsw2_seed_check vectors PREFIX VECTORS.tsv
-//       every line of the golden file (see tools/make_bwasw_golden.py) recomputed and compared;
-//       prints the class counts and "N vectors, D differ".
+//       every line of a golden file (see tools/make_bwasw_golden.py) recomputed and compared;
+//       prints the class counts and "N vectors, D differ".  A vector whose option-set name is
+//       "INDEX/name" runs on the index INDEX that lies next to PREFIX, every other one on PREFIX.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -74,7 +75,14 @@ struct FileIdx {
     }
     if (k >= primary) --k;
     memcpy(cnt, &cp[k / 64 * 4], 16);
-    for (uint32_t i = k / 64 * 64; i <= k; ++i) ++cnt[sym(i)];
+    for (uint32_t i = k / 64 * 64; i <= k; i += 16) {  // 16 symbols a word, the first n of this one
+      const uint32_t n = std::min<uint32_t>(16, k - i + 1), w = bwt[i >> 4] >> (2 * (16 - n));
+      const uint32_t m = n == 16 ? 0x55555555u : ((1u << (2 * n)) - 1u) & 0x55555555u;
+      for (uint32_t c = 0; c < 4; ++c) {
+        const uint32_t x = w ^ (c * 0x55555555u);
+        cnt[c] += (uint32_t)__builtin_popcount(~(x | (x >> 1)) & m);
+      }
+    }
   }
   uint32_t inv_psi(uint32_t k) const {  // bwt_invPsi (bwt.h:66-70)
     if (k == primary) return 0;
@@ -122,11 +130,18 @@ int main(int argc, char **argv) {
     return 2;
   }
   const std::string mode = argv[1], prefix = argv[2];
-  FileIdx idx[2];
-  if (!idx[0].load(prefix + ".bwt", prefix + ".sa") || !idx[1].load(prefix + ".rbwt", prefix + ".rsa")) {
-    fprintf(stderr, "cannot load %s.{bwt,sa,rbwt,rsa}\n", prefix.c_str());
-    return 2;
-  }
+  std::map<std::string, FileIdx[2]> loaded;
+  auto index_at = [&](const std::string &p) -> FileIdx * {
+    auto it = loaded.find(p);
+    if (it != loaded.end()) return it->second;
+    FileIdx *x = loaded[p];
+    if (!x[0].load(p + ".bwt", p + ".sa") || !x[1].load(p + ".rbwt", p + ".rsa")) {
+      fprintf(stderr, "cannot load %s.{bwt,sa,rbwt,rsa}\n", p.c_str());
+      exit(2);
+    }
+    return x;
+  };
+  const FileIdx *idx = index_at(prefix);
   std::ifstream in(argv[3]);
   if (!in) {
     fprintf(stderr, "cannot open %s\n", argv[3]);
@@ -200,6 +215,13 @@ int main(int argc, char **argv) {
     const float coef = strtof(f[9].c_str(), nullptr);
     const int adjust = atoi(f[10].c_str()), strand = atoi(f[13].c_str());
     const std::vector<uint8_t> seq = codes(f[15]);
+    const FileIdx *idx = index_at(prefix);
+    const size_t slash = f[0].find('/');
+    if (slash != std::string::npos) {  // "INDEX/name": the index of that name next to PREFIX
+      const size_t dir = prefix.rfind('/');
+      idx = index_at((dir == std::string::npos ? std::string() : prefix.substr(0, dir + 1)) + f[0].substr(0, slash));
+      ++cls["index:" + f[0].substr(0, slash)];
+    }
     if (adjust) opt_for_len(o.a, o.q, o.r, o.t, o.bw, coef, (uint32_t)seq.size(), &o.t, &o.bw);
     bool bad = o.t != atoi(f[11].c_str()) || o.bw != atoi(f[12].c_str());
     std::vector<Hit> all, narrow;
@@ -213,6 +235,9 @@ int main(int argc, char **argv) {
     ++cls["optset:" + f[0]];
     ++cls["kind:" + f[14]];
     ++cls["len:" + std::to_string(seq.size()) + (strand ? ":r" : ":f")];
+    if (seq.size() >= 2048) ++cls["long:" + f[14]];
+    if (seq.size() > 1000) ++cls["at:" + std::to_string(seq.size()) + ":" + f[14]];
+    if (seq.size() > 1000) cls["hits:" + std::to_string(seq.size())] += !all.empty() || !narrow.empty();
     cls["event:swap"] += c.n_swap > 0;
     cls["event:dup"] += c.n_dup > 0;
     cls["event:tie_cut"] += c.n_tie_cut > 0;

@@ -59,7 +59,8 @@ def test_batch_order_does_not_matter(seed_engine, vectors):
     b = seed_engine.bwasw_seeds([seqs[i] for i in order], [strands[i] for i in order], opt)
     assert [a[i] for i in order] == b
     assert a == [v[5] for v in vs]
-    # and a single wave's worth of work, every task claimed by the same few waves
+    # one wave per CU: still more waves than this batch has tasks, so each claims one task at most;
+    # waves that run many tasks are the matter of tests/test_bsw2_seed_edges_gpu.py
     seed_engine.set_option("seed_waves_per_cu", 1)
     try:
         assert seed_engine.bwasw_seeds(seqs[::-1], strands[::-1], opt) == a[::-1]

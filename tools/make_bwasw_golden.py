@@ -15,6 +15,15 @@ hits: "n_all n_narrow" then every hit as k,l,flag,len,G,G2,beg,end).
 The host restatement (ibwa_amd/csrc/bsw2_core.h through tests/host/bsw2_seed_check.cpp) classifies
 every vector; the file is written only if it reproduces every vector and every class of
 tests/test_bsw2_vectors.py has its count.
+
+Two more files in the same line format, by the same harness, under the same rule:
+  --long   seed_long_vectors.tsv.gz: reads of 1 023 to 8 192 bases on g1m, option sets defaults and
+           z3 (conditions: check_long_classes);
+  --small  seed_small_index_vectors.tsv.gz: the tasks of tests/test_bsw2_core_host.small_index_tasks
+           on the small indexes idx_quirks and csg with at most 1 500 final hits, and with is == 0
+           only those whose all-list the reference returned empty.  Their option-set name is
+           "INDEX/is<is>t<t>z<z>": the part before the slash names the index under tests/golden.
+  --all    all three.
 """
 import gzip
 import os
@@ -100,10 +109,10 @@ KINDS = ("exact", "sub2", "sub5", "sub10", "sub2indel", "sub5indel", "sub10indel
          "polyA", "ACAC", "period3")
 
 
-def load_genome():
-    with open(os.path.join(GOLD, "g1m.pac"), "rb") as f:
+def load_genome(name="g1m"):
+    with open(os.path.join(GOLD, name + ".pac"), "rb") as f:
         pac = f.read()
-    with open(os.path.join(GOLD, "g1m.ann")) as f:
+    with open(os.path.join(GOLD, name + ".ann")) as f:
         n = int(f.readline().split()[0])  # l_pac
     return [pac[i >> 2] >> ((~i & 3) << 1) & 3 for i in range(n)]
 
@@ -213,46 +222,106 @@ def build(tmp):
     return ref, chk
 
 
+LONG_LENGTHS = (1023, 1024, 2047, 2048, 2049, 4095, 4096, 8191, 8192)
+LONG_KINDS = ("sub2", "sub10", "chimera", "random", "period3", "polyA", "ACAC", "period3exact")
+
+
+def make_long_tasks(g):
+    """Every length x kind x option set on .bwt and one row per length on .rbwt: the size limit does
+    not bind (about 175 KB), so nothing is thinned."""
+    rng = random.Random(20261021)
+    tasks = []
+    for ln in LONG_LENGTHS:
+        for kind in LONG_KINDS:
+            for optset in ("defaults", "z3"):
+                s = [i % 3 for i in range(ln)] if kind == "period3exact" else make_read(rng, g, kind, ln)
+                tasks.append((optset, 0, kind, s))
+        k = LONG_LENGTHS.index(ln)
+        kind = ("sub2", "chimera", "period3")[k % 3]
+        tasks.append((("defaults", "z3")[k & 1], 1, kind, make_read(rng, g, kind, ln)[::-1]))
+    return tasks
+
+
+def reference_lines(ref, tmp, index, tasks, optsets):
+    """The vector lines of tasks [(optset, strand, kind, codes)] on tests/golden/<index>."""
+    tf = os.path.join(tmp, "tasks.txt")
+    with open(tf, "w") as f:
+        for optset, strand, _kind, s in tasks:
+            a, b, q, r, t, bw, z, is_, coef, adjust = optsets[optset]
+            f.write(f"{a} {b} {q} {r} {t} {bw} {z} {is_} {coef} {adjust} {strand} {''.join(map(str, s))}\n")
+    out = subprocess.run([ref, os.path.join(GOLD, index), tf], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
+    assert len(out) == len(tasks), (len(out), len(tasks))
+    lines = []
+    for (optset, strand, kind, s), o in zip(tasks, out):
+        tbw, hits = o.split("\t")
+        t, bw = tbw.split()
+        a, b, q, r, t0, bw0, z, is_, coef, adjust = optsets[optset]
+        lines.append("\t".join(map(str, (optset, a, b, q, r, t0, bw0, z, is_, coef, adjust, t, bw, strand, kind,
+                                         "".join(map(str, s)), hits))))
+    return lines
+
+
+SMALL_PER_INDEX = 150  # the first so many tasks that qualify: the size limit of the file
+
+
+def small_index_lines(ref, tmp):
+    from tests.test_bsw2_core_host import SMALL_INDEXES, small_index_tasks
+    lines = []
+    for index in SMALL_INDEXES:
+        optsets, tasks = {}, []
+        for a, b, q, r, t, bw, z, is_, strand, s in small_index_tasks(index):
+            name = f"{index}/is{is_}t{t}z{z}"
+            optsets[name] = (a, b, q, r, t, bw, z, is_, 5.5, 0)
+            kind = "homopolymer" if len(set(s)) == 1 else "other"
+            tasks.append((name, strand, kind, s))
+        kept = 0
+        for line in reference_lines(ref, tmp, index, tasks, optsets):
+            c = line.split("\t")
+            n_all, n_narrow = map(int, c[16].split()[:2])
+            if n_all + n_narrow <= 1500 and (int(c[8]) != 0 or n_all == 0) and kept < SMALL_PER_INDEX:
+                lines.append(line)
+                kept += 1
+    return lines
+
+
+def write_vectors(chk, tmp, out, lines, check):
+    """Write out only if the host restatement reproduces every line and check finds no class short."""
+    from tests.test_bsw2_vectors import parse_classes
+    text = "\n".join(lines) + "\n"
+    plain = os.path.join(tmp, "vectors.tsv")
+    with open(plain, "w") as f:
+        f.write(text)
+    r = subprocess.run([chk, "vectors", os.path.join(GOLD, "g1m"), plain], stdout=subprocess.PIPE, text=True)
+    print(r.stdout)
+    if r.returncode != 0:
+        sys.exit("the host restatement does not reproduce the vectors: nothing written")
+    problems = check(parse_classes(r.stdout))
+    if problems:
+        sys.exit("classes short of their counts, nothing written:\n  " + "\n  ".join(problems))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", filename="", mtime=0, compresslevel=9) as z:
+        z.write(text.encode())
+    size = os.path.getsize(out)
+    print(f"{out}: {len(lines)} vectors, {size} bytes")
+    if size > 256 * 1024:
+        os.remove(out)
+        sys.exit("the file is above 256 KB: removed")
+
+
 def main():
-    from tests.test_bsw2_vectors import check_classes, parse_classes
-    g = load_genome()
-    tasks = make_tasks(g)
-    prefix = os.path.join(GOLD, "g1m")
+    from tests.test_bsw2_vectors import LONG_VECTORS, SMALL_VECTORS, check_classes, check_long_classes, check_small_classes
+    flags = set(sys.argv[1:])
+    if flags - {"--long", "--small", "--all"}:
+        sys.exit("usage: make_bwasw_golden.py [--long] [--small] [--all]")
     with tempfile.TemporaryDirectory() as tmp:
         ref, chk = build(tmp)
-        tf = os.path.join(tmp, "tasks.txt")
-        with open(tf, "w") as f:
-            for optset, strand, _kind, s in tasks:
-                a, b, q, r, t, bw, z, is_, coef, adjust = OPTSETS[optset]
-                f.write(f"{a} {b} {q} {r} {t} {bw} {z} {is_} {coef} {adjust} {strand} {''.join(map(str, s))}\n")
-        out = subprocess.run([ref, prefix, tf], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
-        assert len(out) == len(tasks), (len(out), len(tasks))
-        lines = []
-        for (optset, strand, kind, s), o in zip(tasks, out):
-            tbw, hits = o.split("\t")
-            t, bw = tbw.split()
-            a, b, q, r, t0, bw0, z, is_, coef, adjust = OPTSETS[optset]
-            lines.append("\t".join(map(str, (optset, a, b, q, r, t0, bw0, z, is_, coef, adjust, t, bw, strand, kind,
-                                             "".join(map(str, s)), hits))))
-        text = "\n".join(lines) + "\n"
-        plain = os.path.join(tmp, "vectors.tsv")
-        with open(plain, "w") as f:
-            f.write(text)
-        r = subprocess.run([chk, "vectors", prefix, plain], stdout=subprocess.PIPE, text=True)
-        print(r.stdout)
-        if r.returncode != 0:
-            sys.exit("the host restatement does not reproduce the vectors: nothing written")
-        problems = check_classes(parse_classes(r.stdout))
-        if problems:
-            sys.exit("classes short of their counts, nothing written:\n  " + "\n  ".join(problems))
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        with open(OUT, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", filename="", mtime=0, compresslevel=9) as z:
-            z.write(text.encode())
-    size = os.path.getsize(OUT)
-    print(f"{OUT}: {len(tasks)} vectors, {size} bytes")
-    if size > 256 * 1024:
-        os.remove(OUT)
-        sys.exit("the file is above 256 KB: removed")
+        if not flags or "--all" in flags:
+            write_vectors(chk, tmp, OUT, reference_lines(ref, tmp, "g1m", make_tasks(load_genome()), OPTSETS), check_classes)
+        if flags & {"--long", "--all"}:
+            write_vectors(chk, tmp, LONG_VECTORS, reference_lines(ref, tmp, "g1m", make_long_tasks(load_genome()), OPTSETS),
+                          check_long_classes)
+        if flags & {"--small", "--all"}:
+            write_vectors(chk, tmp, SMALL_VECTORS, small_index_lines(ref, tmp), check_small_classes)
 
 
 if __name__ == "__main__":
