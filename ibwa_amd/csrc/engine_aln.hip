@@ -104,6 +104,8 @@ struct Run {
   double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+size_t first_pass_lds(const Run &R);  // plan_first_pass's LDS bytes per workgroup
+
 // Checks, the batch-level options, the per-length max_diff table and the arguments every pass shares;
 // which path takes the batch.
 int run_setup(Run &R, int batch_max_len) {
@@ -163,9 +165,13 @@ int run_setup(Run &R, int batch_max_len) {
   c->stats.path = R.exact_path ? 1 : 0;
   if (R.exact_path) return 0;
 
-  // persistent gapped search (gapped.hip) when the options fit its entry bit fields
+  // persistent gapped search (gapped.hip) when the options fit its entry bit fields and the bucket
+  // heads fit a workgroup's LDS: one lane's in the wide kernel (4 B heads: n_stacks <= 12 288) and 64
+  // lanes' in the first pass (2 B heads, without the LDS widths one per bucket: n_stacks <= 480 with
+  // the default page settings)
   R.v2 = c->gapped_v2 && batch_md + 1 <= 31 && o.max_gapo <= 7 && o.max_gape <= 15 &&
          gapped_lds_bytes(o.n_stacks, 64, true, 0, 0, 1, 4096) <= 65536 && max_len <= 65535;
+  R.v2 = R.v2 && first_pass_lds(R) <= 65536;
   c->res.stream_out = R.v2;
   c->pass.hpop_valid = false;
   c->res.resumed_ids.clear();
@@ -490,6 +496,8 @@ FirstPassPlan plan_first_pass(const Run &R) {
           rd_cap, aln_total};
 }
 
+size_t first_pass_lds(const Run &R) { return plan_first_pass(R).lds; }
+
 // IBWA_VERBOSE: a k_gapped launch's iterations per read (GapArgs::iters), b ms
 int print_gapped_iters(const uint32_t *d_iters, int64_t cnt, float b) {
   std::vector<uint32_t> it(cnt);
@@ -543,6 +551,8 @@ int first_pass_persistent(Run &R) {
   A.cw_stage = (uint32_t)c->width_rec_stage;
   const FirstPassPlan P = plan_first_pass(R);
   const bool lw = P.lw, resume = P.resume;
+  c->stats.first_pass_lw = lw;
+  c->stats.first_pass_block = P.block;
   const int64_t chunk = P.chunk;
   if (int rc = c->pass.d_wbuf.ensure(chunk * A.wstride * 8)) return rc;
   if (int rc = c->pass.d_nN.ensure(chunk * 2 + 2)) return rc;

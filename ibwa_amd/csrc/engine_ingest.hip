@@ -215,7 +215,7 @@ int ibwa_batch_stage(ibwa_ctx_t *c, int64_t n, const uint8_t *seq, const uint64_
   uint64_t bytes = 0;
   int max_len = 0;
   for (int64_t i = 0; i < n; ++i) {
-    if (len[i] > 65535) return fail(IBWA_EINVAL, "read %lld: length %u > 65535 is not supported", (long long)i, len[i]);
+    if (len[i] > 65535) return fail(IBWA_EINVAL, "read length %u > 65535 is not supported (read %lld)", len[i], (long long)i);
     bytes = std::max<uint64_t>(bytes, off[i] + len[i]);
     max_len = std::max<int>(max_len, (int)len[i]);
   }

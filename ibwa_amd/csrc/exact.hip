@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256) k_pack_reads(const uint8_t *__restrict__ 
     const uint64_t last = off[r0 + nw - 1] + len[r0 + nw - 1];
     span = ((last + 15) & ~(uint64_t)15) - start;
     const bool inside = !act || (o_r >= start && o_r + (uint64_t)L <= start + span);
-    fits = span <= in_cap && __all(inside);
+    fits = in_cap && span <= in_cap && __all(inside);  // (in_cap 0: no LDS at all)
   }
   if (fits) {
     const uint4 *g = reinterpret_cast<const uint4 *>(seq + start);
@@ -336,7 +336,8 @@ hipError_t launch_exact(const AlnArgs &a, const uint4 *o64_0, const uint4 *o64_1
   // LDS per wave: the span of 64 back-to-back reads of the batch's longest length, and 64 records
   uint32_t in_cap = (uint32_t)(((uint64_t)64 * std::max<uint32_t>(a.wlen1 - 1, 1) + 32 + 15) & ~15ull);
   if ((size_t)4 * (in_cap + 64 * stride * 16) > 64 * 1024) in_cap = 0;  // long reads: per-lane loads
-  const size_t lds = (size_t)4 * (in_cap + 64 * stride * 16);
+  // (which touch no LDS: the records alone of reads over 960 bases would not fit a workgroup's either)
+  const size_t lds = in_cap ? (size_t)4 * (in_cap + 64 * stride * 16) : 0;
   hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)((a.n + 255) / 256)), dim3(256), lds, st, a.seq, a.off, a.len, a.n,
                      rec, stride, K, comp, in_cap);
   hipError_t e = hipGetLastError();

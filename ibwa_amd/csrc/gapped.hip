@@ -67,7 +67,9 @@ constexpr int STATE_G = 3;
 // per-lane LDS stack of popped slots awaiting reuse (the retry pass's heavy reads get more)
 constexpr int NARROW_FREE_DEPTH = 8;
 constexpr int LW_FREE_DEPTH = 4;  // LDS-width variant: 8 B per lane
-constexpr int MAX_BUCKETS = 128;  // non-empty-bucket bitmask: four 32-bit registers
+// non-empty-bucket bitmask: four 32-bit registers; the buckets from MAX_BUCKETS on (options with
+// n_stacks > 128) have no bit and are found by their heads
+constexpr int MAX_BUCKETS = 128;
 // first pass: a read of <= 16 * RDW bases without N is kept 2-bit packed in LDS, so the read
 // symbol of an iteration is an LDS access instead of one more HBM line request
 constexpr int RDW = 8;
@@ -691,6 +693,10 @@ __device__ __forceinline__ void gapped_body(const GapArgs &A, unsigned long long
         } else {
           bm_clr(nonempty, C_b);
           b = bm_next(nonempty, C_b + 1);
+          // bm_next's "none" is MAX_BUCKETS, a real bucket when n_stacks > 128 (its empty head would be
+          // loaded as a slot): the buckets past the mask are found by their heads, n_stacks when none
+          if (b >= MAX_BUCKETS && o.n_stacks > MAX_BUCKETS)
+            for (b = C_b + 1 > MAX_BUCKETS ? C_b + 1 : MAX_BUCKETS; b < o.n_stacks && lds_heads[hidx(b)] == (H)NILH; ++b) {}
         }
         if (b < o.n_stacks) {
           load_slot = lds_heads[hidx(b)];

@@ -36,7 +36,8 @@ class RunStats(c.Structure):
                 ("resume_records_peak", c.c_int64), ("resume_records_cap", c.c_int64),
                 ("coop_pages_peak", c.c_int64), ("coop_pages_cap", c.c_int64), ("ms_alloc", c.c_double),
                 ("n_tail_jumps", c.c_int64), ("n_width_tab_steps", c.c_int64),
-                ("ms_bsw2_seed", c.c_double), ("n_bsw2_retry", c.c_int64), ("bsw2_arena_peak", c.c_int64)]
+                ("ms_bsw2_seed", c.c_double), ("n_bsw2_retry", c.c_int64), ("bsw2_arena_peak", c.c_int64),
+                ("first_pass_lw", c.c_int), ("first_pass_block", c.c_int)]
 
 
 class RefSeq(c.Structure):

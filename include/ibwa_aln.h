@@ -224,6 +224,9 @@ typedef struct {
 	double ms_bsw2_seed;         /* last ibwa_bsw2_seed_batch: k_bsw2_seed kernel time, its retry launch included */
 	int64_t n_bsw2_retry;        /* ... tasks that outgrew their arena or the output buffer and ran again */
 	int64_t bsw2_arena_peak;     /* ... the largest arena a task used, in bytes */
+	int first_pass_lw;           /* 1: the persistent first pass ran in its LDS-width variant (width records and a
+	                                ring of 16 bucket heads in LDS), 0: it did not, or path != 2 */
+	int first_pass_block;        /* its workgroup size, 256 / 128 / 64 (0: the persistent kernel did not run) */
 } ibwa_run_stats_t;
 int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
 
