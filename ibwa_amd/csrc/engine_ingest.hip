@@ -133,7 +133,9 @@ int ibwa_fq_parse(ibwa_ctx_t *c, const void *raw, uint64_t nbytes, int mode, int
   const uint64_t complete = cnt[0] / 4;
   uint64_t n = std::min<uint64_t>(complete, cnt[1]);
   *not_strict = cnt[1] < complete && n == cnt[1];
-  if (n > (uint64_t)cap) {  // the caller takes at most cap records: the block ends at the last of them
+  // the caller takes at most cap records: the block ends at the last of them, and a record past
+  // them is not reported on (cap records that end right before a bad one included)
+  if (n >= (uint64_t)cap) {
     n = (uint64_t)cap;
     *not_strict = 0;
   }
@@ -186,6 +188,29 @@ int ibwa_fq_offset(const ibwa_ctx_t *c, int64_t r, uint64_t *off) {
 int ibwa_fq_stats(const ibwa_ctx_t *c, int64_t *kept, double *ms) {
   if (kept) *kept = c->fq_kept;
   if (ms) *ms = c->fq_ms;
+  return 0;
+}
+
+int ibwa_fq_fetch(const ibwa_ctx_t *c, int64_t first, int64_t n, uint32_t *len, uint64_t *off, uint8_t *codes,
+                  uint64_t codes_cap) {
+  if (!c || !len || !off || !codes) return fail(IBWA_EINVAL, "fq_fetch: null pointer");
+  if (first < 0 || n < 0 || first > c->fq_kept || n > c->fq_kept - first)
+    return fail(IBWA_EINVAL, "fq_fetch: reads [%lld, %lld) outside the %lld kept reads of the parsed block",
+                (long long)first, (long long)(first + n), (long long)c->fq_kept);
+  if (n == 0) return 0;
+  HIPCHK(enter(c));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(len, c->fq_lenk.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(off, c->fq_offk.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost));
+  // the kept reads lie in the code array in order, one behind the other
+  const uint64_t lo = off[0], hi = off[n - 1] + len[n - 1];
+  if (hi < lo || hi > c->fq_codes.cap)
+    return fail(IBWA_EINVAL, "fq_fetch: offsets [%llu, %llu) outside the block's %llu code bytes", (unsigned long long)lo,
+                (unsigned long long)hi, (unsigned long long)c->fq_codes.cap);
+  if (hi - lo > codes_cap)
+    return fail(IBWA_EINVAL, "fq_fetch: %llu code bytes, room for %llu", (unsigned long long)(hi - lo),
+                (unsigned long long)codes_cap);
+  if (hi > lo) HIPCHK(hipMemcpy(codes, c->fq_codes.as<uint8_t>() + lo, hi - lo, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -89,7 +89,8 @@ CAPI = {
     "ibwa_fq_parse": (_i, [_vp, _vp, c.c_uint64, _i, _i, c.POINTER(c.c_int64), c.POINTER(c.c_uint64), c.POINTER(_i),
                            _vp, _vp, c.c_int64]),
     "ibwa_fq_stats": (_i, [_vp, c.POINTER(c.c_int64), c.POINTER(c.c_double)]),
-    "ibwa_fq_offset": (_i, [_vp, c.c_int64, c.POINTER(c.c_uint64)]),
+    "ibwa_fq_fetch": (_i, [_vp, c.c_int64, c.c_int64, _vp, _vp, _vp, c.c_uint64]),
+    "ibwa_fq_offset": (_i,[_vp, c.c_int64, c.POINTER(c.c_uint64)]),
     "ibwa_fq_share_scratch": (_i, [_vp, _vp]),
     "ibwa_release": (_i, [_i]),
     "ibwa_batch_fetch_sai": (_i, [_vp, _vp, c.c_uint64, c.POINTER(c.c_uint64), c.POINTER(c.c_int64)]),
@@ -409,6 +410,60 @@ class Engine:
         s, o, l = self._keep
         _chk(lib().ibwa_batch_stage(self.h, l.size, s.ctypes.data, o.ctypes.data, l.ctypes.data))
         self.n = l.size
+
+    def fq_parse(self, raw, barcode=0, trim_qual=0, il13=False, cap=None):
+        """ibwa_fq_parse over one raw block (bytes, or a uint8 array -- e.g. a view of ibwa_host_alloc memory):
+        (n_rec, consumed, not_strict, rec_len int32[n_rec], rec_L uint32[n_rec]).  cap=None: the CLI's
+        len(raw) // 48 + 17 (ingest.h).  The kept reads stay in the context (fq_kept, stage_fq)."""
+        if isinstance(raw, np.ndarray):
+            a = np.ascontiguousarray(raw, dtype=np.uint8)
+        else:
+            a = np.frombuffer(bytes(raw) or b"\0", dtype=np.uint8)
+        nbytes = len(raw)
+        if cap is None:
+            cap = nbytes // 48 + 17
+        n_rec, consumed, not_strict = c.c_int64(), c.c_uint64(), c.c_int()
+        rec_len = np.zeros(max(cap, 1), np.int32)
+        rec_L = np.zeros(max(cap, 1), np.uint32)
+        mode = (int(barcode) << 24) | (MODE_IL13 if il13 else 0)
+        _chk(lib().ibwa_fq_parse(self.h, a.ctypes.data, nbytes, mode, int(trim_qual), c.byref(n_rec), c.byref(consumed),
+                                 c.byref(not_strict), rec_len.ctypes.data, rec_L.ctypes.data, cap))
+        self._fq_nbytes = nbytes
+        n = n_rec.value
+        return n, consumed.value, not_strict.value, rec_len[:n].copy(), rec_L[:n].copy()
+
+    def fq_stats(self):
+        """(kept reads, device ms) of the last fq_parse (ibwa_fq_stats)."""
+        kept, ms = c.c_int64(), c.c_double()
+        _chk(lib().ibwa_fq_stats(self.h, c.byref(kept), c.byref(ms)))
+        return kept.value, ms.value
+
+    def fq_offset(self, r):
+        """Byte offset of record r in the last parsed block (ibwa_fq_offset)."""
+        off = c.c_uint64()
+        _chk(lib().ibwa_fq_offset(self.h, int(r), c.byref(off)))
+        return off.value
+
+    def fq_kept(self, first=0, n=None):
+        """Kept reads [first, first + n) of the last parsed block as the device holds them (ibwa_fq_fetch):
+        (codes uint8 -- the bytes the reads span, off uint64[n] -- absolute, lens uint32[n]).  n=None: to the last."""
+        if n is None:
+            n = self.fq_stats()[0] - first
+        lens = np.zeros(max(n, 1), np.uint32)
+        off = np.zeros(max(n, 1), np.uint64)
+        codes = np.zeros(getattr(self, "_fq_nbytes", 0) // 2 + 16, np.uint8)
+        _chk(lib().ibwa_fq_fetch(self.h, int(first), int(n), lens.ctypes.data, off.ctypes.data, codes.ctypes.data,
+                                 codes.size))
+        n = max(n, 0)
+        lens, off = lens[:n], off[:n]
+        nb = int(off[-1] + lens[-1] - off[0]) if n else 0
+        return codes[:nb].copy(), off.copy(), lens.copy()
+
+    def stage_fq(self, src, first, n, max_len):
+        """Stage kept reads [first, first + n) of src's last parsed block as this context's batch
+        (ibwa_batch_stage_fq: a view, nothing is copied)."""
+        _chk(lib().ibwa_batch_stage_fq(self.h, src.h, int(first), int(n), int(max_len)))
+        self.n = int(n)
 
     def run(self, opt, batch_max_len=0):
         _chk(lib().ibwa_batch_run(self.h, c.byref(opt), batch_max_len))

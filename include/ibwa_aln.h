@@ -145,7 +145,7 @@ int ibwa_batch_stage(ibwa_ctx_t *ctx, int64_t n_seqs, const uint8_t *seq, const 
  * reversal (:197).  raw[0, nbytes) must begin at a record.  Out: *n_rec strict records from its
  * start (at most cap), the *consumed bytes they span, *not_strict = 1 when the next complete
  * record is not strict (the serial kseq reader takes over there; else the block ended inside a
- * record), per record the kept length (-1: not longer than the barcode, skipped as bwaseqio.c:162)
+ * record, or *n_rec == cap: what follows the cap records is not reported on), per record the kept length (-1: not longer than the barcode, skipped as bwaseqio.c:162)
  * and the sequence line's length (rec_len / rec_L may be null).  The kept reads stay in the
  * context (one block at a time) for ibwa_batch_stage_fq.  raw may be pinned (ibwa_host_alloc).
  */
@@ -160,6 +160,15 @@ int ibwa_fq_offset(const ibwa_ctx_t *ctx, int64_t r, uint64_t *off);
 int ibwa_fq_share_scratch(ibwa_ctx_t *dst, const ibwa_ctx_t *src);
 /* kept reads and device time (H2D copy + kernels, ms) of the last ibwa_fq_parse */
 int ibwa_fq_stats(const ibwa_ctx_t *ctx, int64_t *kept, double *ms);
+/* Diagnostic accessor (tests): the kept reads [first, first + n) of ctx's last parsed block, copied to
+ * the host as the device holds them -- len[n], off[n] (absolute offsets into the block's code array;
+ * the kept reads lie there one behind the other from 0) and into codes the bytes they span,
+ * off[n-1] + len[n-1] - off[0] of them (at most codes_cap, else IBWA_EINVAL; half the block's bytes
+ * always suffice).  Waits for ctx's stream and launches nothing.  The kept reads are the context's own,
+ * so this also holds after another context has parsed through a shared scratch.  IBWA_EINVAL for a
+ * range outside the ibwa_fq_stats kept reads and for null pointers. */
+int ibwa_fq_fetch(const ibwa_ctx_t *ctx, int64_t first, int64_t n, uint32_t *len, uint64_t *off, uint8_t *codes,
+                  uint64_t codes_cap);
 /* ibwa_batch_stage from src's last parsed block (same device): its kept reads [first, first + n),
  * max_len = their longest.  Nothing is copied: the batch is a view of src's block, which must not be
  * parsed over (ibwa_fq_parse on src) or destroyed while this context runs or fetches the batch. */
