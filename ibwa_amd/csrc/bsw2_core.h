@@ -126,15 +126,17 @@ struct Bwtl {
 // ---- bsw2_resolve_duphits with an index (bwtsw2_core.c:261-327) ----
 // The second half (:295-326): the unstable sort by G, then every hit contained in a better one goes.
 // b is the expanded array, one element per SA row, G == 0 for the rows of empty slots.
-inline void finish_duphits(std::vector<Hit> &b, std::vector<Hit> &out) {
-  ibwa_sam::ks_introsort(b.size(), b.data(), [](const Hit &x, const Hit &y) { return x.G > y.G; });
+// H: Hit, or bsw2_aln1.h's AlnHit, which carries n_seeds.
+template <class H>
+inline void finish_duphits(std::vector<H> &b, std::vector<H> &out) {
+  ibwa_sam::ks_introsort(b.size(), b.data(), [](const H &x, const H &y) { return x.G > y.G; });
   const int bn = (int)b.size();
   int i;
   for (i = 1; i < bn; ++i) {
-    Hit *p = &b[i];
+    H *p = &b[i];
     if (p->G == 0) break;
     for (int j = 0; j < i; ++j) {
-      const Hit *q = &b[j];
+      const H *q = &b[j];
       bool compatible = true;
       if (q->G == 0) continue;
       if (p->l == 0 && q->l == 0) {

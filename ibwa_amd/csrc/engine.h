@@ -448,6 +448,35 @@ struct SeedArgs {
 };
 hipError_t launch_seed(const SeedArgs &a, int blocks, hipStream_t st);
 
+// bwasw's extensions over hit lists (bsw2_extend.hip): bsw2_extend_left in dependency order, one list
+// per persistent wave, or (ordered == 0) bsw2_extend_rght, whose hits are independent, 64 hits of any
+// lists per claim.
+struct Bsw2ExtArgs {
+  const uint32_t *pac;       // the resident sequence (refine.hip's layout)
+  uint64_t l_pac;
+  int64_t n_tasks;           // lists
+  const uint8_t *qry;        // per task the sequence the DP reads: left, the strand's sequence reversed; right, as it is
+  const uint64_t *qoff;
+  const uint32_t *qlen;
+  const int32_t *bw;         // per task, already derived from the read's length
+  const uint8_t *is_rev;     // per task: target bases through __rpac
+  const uint64_t *hoff;      // per task: its first hit; hoff[n_tasks] = n_hits
+  uint32_t *hits;            // ibwa_bsw2_aln_hit_t records (9 words), updated in place
+  const uint32_t *htask;     // ordered == 0: the task of each hit
+  int64_t n_hits;
+  int ordered;
+  int a, b, q, r;
+  uint8_t *tgt;              // per wave 64 target windows of tgt_bytes bytes, a lane's window contiguous
+  uint32_t tgt_bytes;
+  uint32_t *eh;              // per wave 64 * eh_words ring words, lane-minor, for the rings past lds_ring
+  uint32_t eh_words, lds_ring;
+  uint32_t *status;          // per task: 0, or 1 when a window or a ring did not fit what the launcher sized
+  unsigned long long *ctr;   // claim, then 6 counts: DP runs kept, hits contained before any DP, DP runs
+                             // discarded, hits skipped (l != 0 or k == 0), lists, windows
+};
+uint32_t bsw2_extend_lds_bytes(const Bsw2ExtArgs &a);
+hipError_t launch_bsw2_extend(const Bsw2ExtArgs &a, bool all_lds, int waves, hipStream_t st);
+
 hipError_t build_kmer_table(const IndexView &ix, int K, uint2 *table, uint2 *tmp, hipStream_t st);
 // first index of level d of a level table: (4^d - 1) / 3 rounded up to a multiple of 4 (level d >= 1 then
 // starts 32 B-aligned, so a node's four children are one aligned 32 B load)

@@ -330,6 +330,7 @@ int ibwa_ctx_set_option(ibwa_ctx_t *c, const char *key, long value) {
   else if (k == "stdaln_scratch_mb" && value >= 1 && value <= (1l << 18)) c->stdaln_scratch_mb = value;
   else if (k == "seed_arena_cells" && value >= 0 && value <= (1l << 26)) c->seed_arena_cells = value;
   else if (k == "seed_waves_per_cu" && value >= 1 && value <= 8) c->seed_waves_per_cu = (int)value;
+  else if (k == "bsw2_ext_waves_per_cu" && value >= 0 && value <= 8) c->bsw2_ext_waves_per_cu = (int)value;
   else return fail(IBWA_EINVAL, "unknown option %s", k.c_str());
   return 0;
 }

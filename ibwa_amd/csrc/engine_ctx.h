@@ -233,6 +233,10 @@ struct StdBufs {
 struct SeedBufs {
   DBuf seq, off, len, strand, t, bw, ids, arena, res, out, ctr;
 };
+// the buffers of k_bsw2_extend's launches (ibwa_bsw2_aln1_batch, ibwa_bsw2_extend_left_batch; kept between calls).
+struct Bsw2ExtBufs {
+  DBuf qry, qoff, qlen, bw, rev, hoff, hits, htask, tgt, eh, status, ctr;
+};
 // ibwa_refine_batch's own buffers.  ibwa_pac_extract borrows them for its begins, lengths and got
 // counts (dpos, dext, dout in that order).
 struct RefineBufs {
@@ -269,6 +273,7 @@ struct ibwa_ctx : ibwa::CtxQueue {
   ibwa::SwBufs sw;
   ibwa::StdBufs sd;
   ibwa::SeedBufs seed;
+  ibwa::Bsw2ExtBufs bext;
   ibwa::RefineBufs rf;
   ibwa::MdBufs md;
   ibwa::CsBufs cs;
@@ -354,6 +359,8 @@ struct ibwa_ctx : ibwa::CtxQueue {
   int64_t seed_arena_cells = 0;      // option: cells of a task's arena in k_bsw2_seed's first launch (0: by read length)
   int seed_waves_per_cu = 8;         // option: its persistent waves per CU (18 KiB of LDS each)
   int64_t seed_stats[8] = {};        // ibwa_bsw2_seed_stats
+  int bsw2_ext_waves_per_cu = 0;     // option: k_bsw2_extend's persistent waves per CU (0: what the LDS admits, 8 at most)
+  int64_t aln1_stats[8] = {};        // ibwa_bsw2_aln1_stats
   int64_t extend_no_band = 0;        // path-mode pairs of the last extension whose global fill stayed below the extension score
   int diag = 0;                      // option: keep per-read first-pass iterations and k_width features
   uint32_t gap_stream_per_read = 4;     // first-pass hit-stream slots per read

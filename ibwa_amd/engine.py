@@ -153,6 +153,11 @@ CAPI = {
     "ibwa_bsw2_seed_check": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "ibwa_bsw2_opt_for_len": (None, [_vp, _u32, c.POINTER(c.c_int32), c.POINTER(c.c_int32)]),
     "ibwa_bsw2_seed_stats": (_i, [_vp, c.POINTER(c.c_int64 * 8)]),
+    "ibwa_bsw2_aln_opt_preset": (_i, [c.c_char_p, _vp]),
+    "ibwa_bsw2_aln1_batch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
+    "ibwa_bsw2_extend_left_batch": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_bsw2_aln1_check": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ibwa_bsw2_aln1_stats": (_i, [_vp, c.POINTER(c.c_int64 * 8)]),
     "ibwa_ctx_load_pac": (_i, [_vp, _i, c.POINTER(_vp), c.POINTER(_u64)]),
     "ibwa_pac_extract": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ibwa_refine_batch": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c.POINTER(c.c_void_p), c.POINTER(_i64)]),
@@ -269,6 +274,45 @@ def bsw2_opt(opt="bwasw", adjust=None, **kw):
     if adjust is not None:
         o.adjust = 1 if adjust else 0
     return o
+
+
+class Bsw2AlnOpt(c.Structure):
+    """ibwa_bsw2_aln_opt_t: the seeding's options, then bsw2opt_t's t_seeds and mask_level."""
+    _fields_ = [("seed", Bsw2Opt), ("t_seeds", c.c_int32), ("mask_level", c.c_float)]
+
+
+BSW2_ALN_HIT_DTYPE = np.dtype([("k", "<u4"), ("l", "<u4"), ("flag", "<u4"), ("n_seeds", "<u4"), ("len", "<i4"), ("G", "<i4"),
+                               ("G2", "<i4"), ("beg", "<i4"), ("end", "<i4")])  # ibwa_bsw2_aln_hit_t
+
+
+def bsw2_aln_opt(opt="bwasw", adjust=None, **kw):
+    """As bsw2_opt, with the keys t_seeds and mask_level besides ("bwasw": 5 and 0.50) -> Bsw2AlnOpt."""
+    if isinstance(opt, Bsw2AlnOpt):
+        o = Bsw2AlnOpt.from_buffer_copy(opt)
+        opt = o.seed
+    else:
+        o = Bsw2AlnOpt()
+        _chk(lib().ibwa_bsw2_aln_opt_preset((opt if isinstance(opt, str) else "bwasw").encode(), c.byref(o)))
+        if isinstance(opt, dict):
+            kw = dict(opt, **kw)
+            opt = "bwasw"
+    for k in ("t_seeds", "mask_level"):
+        if k in kw:
+            setattr(o, k, kw.pop(k))
+    o.seed = bsw2_opt(opt, adjust, **kw)
+    return o
+
+
+def bsw2_aln1_check(seqs, is_rev, opt="bwasw", adjust=None, u=None):
+    """The checks of ibwa_bsw2_aln1_batch alone (no device): raises IbwaError on a refusal."""
+    o = bsw2_aln_opt(opt, adjust)
+    s, off, ln = Engine._pack_reads(seqs)
+    rv = np.ascontiguousarray(is_rev, dtype=np.uint8)
+    uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    if rv.size != ln.size or (uu is not None and uu.size != ln.size):
+        raise IbwaError("bsw2 aln1: seqs, is_rev and u differ in length")
+    _chk(lib().ibwa_bsw2_aln1_check(c.byref(o), ln.size, s.ctypes.data, off.ctypes.data, ln.ctypes.data, rv.ctypes.data,
+                                    None if uu is None else uu.ctypes.data))
 
 
 def bsw2_opt_for_len(opt, length):
@@ -773,6 +817,69 @@ class Engine:
             out.append((hits[at:at + a], hits[at + a:at + a + b]))
             at += a + b
         return out
+
+    def bwasw_hits(self, seqs, is_rev, opt="bwasw", adjust=True, u=None):
+        """bwasw from reads to hits on one index strand (ibwa_bsw2_aln1_batch): bsw2_aln1_core of every read
+        -- seqs[i], codes 0-3, against .bwt / .sa with the target read forwards (is_rev[i] == 0), or the
+        reversed read against .rbwt / .rsa with the target read through __rpac (1).  opt: see bsw2_aln_opt;
+        u: per read the draw of bsw2_resolve_query_overlaps in [0, 1) (None: 0.0).  Returns per read the
+        list of (k, l, flag, n_seeds, len, G, G2, beg, end) tuples in the reference's order."""
+        o = bsw2_aln_opt(opt, adjust)
+        s, off, ln = self._pack_reads(seqs)
+        rv = np.ascontiguousarray(is_rev, dtype=np.uint8)
+        uu = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+        n = ln.size
+        if rv.size != n or (uu is not None and uu.size != n):
+            raise IbwaError("bsw2 aln1: seqs, is_rev and u differ in length")
+        cnt = np.zeros(n, np.int32)
+        ptr = c.c_void_p()
+        tot = c.c_int64()
+        _chk(lib().ibwa_bsw2_aln1_batch(self.h, c.byref(o), n, s.ctypes.data, off.ctypes.data, ln.ctypes.data, rv.ctypes.data,
+                                        None if uu is None else uu.ctypes.data, cnt.ctypes.data, c.byref(ptr), c.byref(tot)))
+        try:
+            buf = (c.c_char * (tot.value * BSW2_ALN_HIT_DTYPE.itemsize)).from_address(ptr.value) if tot.value else b""
+            hits = [tuple(int(x) for x in h) for h in np.frombuffer(buf, dtype=BSW2_ALN_HIT_DTYPE).tolist()]
+        finally:
+            lib().ibwa_free(ptr)
+        out, at = [], 0
+        for i in range(n):
+            out.append(hits[at:at + int(cnt[i])])
+            at += int(cnt[i])
+        return out
+
+    def bwasw_extend_left(self, queries, bws, is_rev, hit_lists, opt="bwasw"):
+        """bsw2_extend_left alone (ibwa_bsw2_extend_left_batch): per task a query (the strand's sequence, codes
+        0-3), a band, is_rev and a list of (k, l, flag, n_seeds, len, G, G2, beg, end) in any order.  Returns
+        per task the list sorted by end, descending, with G, len, beg, k and n_seeds as the reference leaves
+        them.  Of opt only a, b, q, r are read."""
+        o = bsw2_opt(opt)
+        s, off, ln = self._pack_reads(queries)
+        n = ln.size
+        bw = np.ascontiguousarray(bws, dtype=np.int32)
+        rv = np.ascontiguousarray(is_rev, dtype=np.uint8)
+        if bw.size != n or rv.size != n or len(hit_lists) != n:
+            raise IbwaError("bsw2 extend_left: queries, bws, is_rev and hit_lists differ in length")
+        cnt = np.array([len(h) for h in hit_lists], np.int32)
+        flat = [tuple(h) for hs in hit_lists for h in hs]
+        hits = np.array(flat, dtype=BSW2_ALN_HIT_DTYPE) if flat else np.zeros(1, BSW2_ALN_HIT_DTYPE)
+        _chk(lib().ibwa_bsw2_extend_left_batch(self.h, c.byref(o), n, s.ctypes.data, off.ctypes.data, ln.ctypes.data,
+                                               bw.ctypes.data, rv.ctypes.data, cnt.ctypes.data, hits.ctypes.data))
+        rows = [tuple(int(x) for x in h) for h in hits.tolist()] if flat else []
+        out, at = [], 0
+        for i in range(n):
+            out.append(rows[at:at + int(cnt[i])])
+            at += int(cnt[i])
+        return out
+
+    def bwasw_hits_stats(self):
+        """The last bwasw_hits or bwasw_extend_left call: microseconds of the left and the right launch; of
+        the left launch the hits extended (DP runs that counted), those skipped as contained before any
+        DP, the speculative DP runs discarded, the hits skipped for l != 0 or k == 0, its tasks and its
+        windows of 64."""
+        v = (c.c_int64 * 8)()
+        _chk(lib().ibwa_bsw2_aln1_stats(self.h, c.byref(v)))
+        return dict(zip(("us_left", "us_right", "extended", "contained", "discarded", "skipped", "tasks", "windows"),
+                        [int(x) for x in v]))
 
     def seed_stats(self):
         """The last bwasw_seeds call: wall-clock ticks its waves spent in bwtl build, traversal and resolve,

@@ -303,6 +303,7 @@ int ibwa_batch_stats(const ibwa_ctx_t *ctx, ibwa_run_stats_t *st);
  *   "seed_arena_cells" (0), "seed_waves_per_cu" (8)  ibwa_bsw2_seed_batch: cells (64 B) of a task's arena in
  *                                  the first launch (0: from the read length; a task that does
  *                                  not fit runs again in a larger arena) and its persistent waves per CU
+ *   "bsw2_ext_waves_per_cu" (0)    k_bsw2_extend's persistent waves per CU (0: as many as the LDS admits, 8 at most)
  *   Test and diagnostics hooks: "gap_stream_per_read" (4), "gap_stream_min" (1 << 20) the first
  *   pass's hit-stream size; "gap_resume_records", "coop_pool_pages" buffer sizes in records / pages;
  *   "diag" (0) per-read iterations and k_width features; "diag_width" (0) keep the first-pass
@@ -666,6 +667,57 @@ void ibwa_bsw2_opt_for_len(const ibwa_bsw2_opt_t *opt, uint32_t len, int32_t *t,
  * resolving, out[3] cells visited, out[4] tasks run again, out[5] the largest arena a task used (bytes),
  * out[6] the first launch's arena per task (bytes), out[7] its workgroups. */
 int ibwa_bsw2_seed_stats(const ibwa_ctx_t *ctx, int64_t out[8]);
+
+/*
+ * bwasw from a read to its hits on one index strand: bsw2_aln1_core (bwtsw2_aux.c:252-276), batched.
+ *
+ * Read i is seq[off[i] .. off[i] + len[i]), codes 0-3; the library builds its reverse complement.  With
+ * is_rev[i] == 0 it is searched against .bwt / .sa and the target bases are read forwards; with 1 against
+ * .rbwt / .rsa and through __rpac, and the caller passes what bsw2_aln_core calls rseq[0], the reversed read.
+ * opt->seed is what ibwa_bsw2_seed_batch takes (t and bw per read when adjust != 0); t_seeds and mask_level
+ * are bsw2opt_t's.  u[i] in [0, 1) stands for the drand48() of bsw2_resolve_query_overlaps (NULL: 0.0).
+ *
+ * Stages, each one launch over the whole batch: the seeds of 2n tasks (ibwa_bsw2_seed_batch); on the host,
+ * bsw2_chain_filter and the sort by end; bsw2_extend_left in dependency order on the device
+ * (k_bsw2_extend, one list per wave); on the host, merge_hits and bsw2_resolve_duphits; bsw2_extend_rght
+ * on the device (the same kernel, unordered); on the host, the strand merge and
+ * bsw2_resolve_query_overlaps.  The host stages are bsw2_aln1.h's functions, run per read on up to 16
+ * threads.  Every field of every hit equals the reference's; *hits = malloc'd (ibwa_free), read i's
+ * n_hits[i] hits in the reference's order, l == 0, flag & 0x10 for a hit of the reverse complement.
+ *
+ * Not part of this call: bsw2_aln_core's second pass and flag_fr, its drand48 fill of ambiguous bases,
+ * CIGARs and SAM.
+ *
+ * IBWA_ENOINDEX without the strand's index and suffix array or without the resident sequence
+ * (ibwa_ctx_load_pac).  IBWA_EINVAL, naming the read, for what ibwa_bsw2_seed_check refuses, for
+ * t_seeds < 0, mask_level outside [0, 1], u outside [0, 1), is_rev > 1, and for a narrow hit whose score
+ * is past 32000, the extension's 16-bit cells.  IBWA_EOVERFLOW, naming the task, when a window or a ring
+ * did not fit what the launch was sized for.  n == 0 returns 0.
+ *
+ * ibwa_bsw2_extend_left_batch is the left stage alone: per task a query qry[off[t] .. +len[t]) (the strand's
+ * sequence as bsw2_extend_left receives it), a band bw[t], is_rev[t] and n_hits[t] hits in the caller's
+ * order, concatenated in hits; the sort by end is inside, and the same list comes back in sorted order
+ * with G, len, beg, k and n_seeds updated.  Of opt only a, b, q, r are read.  IBWA_EINVAL for a hit with
+ * beg outside [0, len], and, where l == 0 and k != 0, k > l_pac or G outside 1..32000.
+ */
+typedef struct { ibwa_bsw2_opt_t seed; int32_t t_seeds; float mask_level; } ibwa_bsw2_aln_opt_t;
+typedef struct { uint32_t k, l, flag, n_seeds; int32_t len, G, G2, beg, end; } ibwa_bsw2_aln_hit_t;
+/* "bwasw": ibwa_bsw2_opt_preset's values, t_seeds 5, mask_level 0.50 */
+int ibwa_bsw2_aln_opt_preset(const char *name, ibwa_bsw2_aln_opt_t *opt);
+int ibwa_bsw2_aln1_batch(ibwa_ctx_t *ctx, const ibwa_bsw2_aln_opt_t *opt, int64_t n, const uint8_t *seq,
+                         const uint64_t *off, const uint32_t *len, const uint8_t *is_rev, const double *u,
+                         int32_t *n_hits, ibwa_bsw2_aln_hit_t **hits, int64_t *n_hits_total);
+int ibwa_bsw2_extend_left_batch(ibwa_ctx_t *ctx, const ibwa_bsw2_opt_t *opt, int64_t n, const uint8_t *qry,
+                                const uint64_t *off, const uint32_t *len, const int32_t *bw, const uint8_t *is_rev,
+                                const int32_t *n_hits, ibwa_bsw2_aln_hit_t *hits);
+/* The argument checks of ibwa_bsw2_aln1_batch alone (no device is touched). */
+int ibwa_bsw2_aln1_check(const ibwa_bsw2_aln_opt_t *opt, int64_t n, const uint8_t *seq, const uint64_t *off,
+                         const uint32_t *len, const uint8_t *is_rev, const double *u);
+/* The last ibwa_bsw2_aln1_batch or ibwa_bsw2_extend_left_batch: out[0], out[1] microseconds of the left and
+ * the right launch; of the left launch out[2] hits extended (DP runs whose result counted), out[3] hits
+ * skipped as contained before any DP, out[4] speculative DP runs discarded, out[5] hits skipped for
+ * l != 0 or k == 0 (out[2..5] add up to its hits), out[6] its tasks, out[7] its windows of 64. */
+int ibwa_bsw2_aln1_stats(const ibwa_ctx_t *ctx, int64_t out[8]);
 
 /* Device Occ KAT: bwt_occ4 (bwt.c:157) for n positions k[] on strand s -> cnt[4*n] */
 int ibwa_occ4(ibwa_ctx_t *ctx, int strand, int64_t n, const uint32_t *k, uint32_t *cnt);
